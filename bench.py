@@ -15,9 +15,16 @@ MirroredStrategy using every visible GPU without a launcher (gpu_utils.py:13-14)
 world size must equal --gpus. `--device cpu --backend gloo` is a dry run of that launcher and of the
 barrier / max-over-ranks timing with a no-op step (no GPU, no kernels; the line says "dry_run").
 
-Also reported: roofline of the fused kernel (algorithmic bytes / HIP-event kernel time vs 8 TB/s),
-PMC-measured HBM traffic when profiles/ holds it for this workload, and the CPU baseline (the C
-oracle — the "port" of the reference semantics — on a bounded sample, rank 0, N=1 only).
+Also reported: roofline of the fused kernel (algorithmic bytes / HIP-event kernel time vs 8 TB/s) and
+PMC-measured HBM traffic when profiles/ holds it for this workload.
+
+A plain run (`--gpus N --steps K --warmup W`) does only what the headline needs: set-up, W untimed and K
+timed steps, the result line. `--full` adds every other leg to the same line: the measured peaks (STREAM
+copy, random-row gather), the uniform-id leg, the CPU baseline (the C oracle — the "port" of the reference
+semantics — on a bounded sample, rank 0, N=1 only), the cfg1-cfg5 extras, the feature pipe and the training
+steps. `--dump-outputs DIR` writes what the last timed step computed to DIR/pooled.npy (float32; a fixed
+seeded sample of its rows when the whole matrix is over 64 MB); inputs are seeded, so two builds run with
+the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -65,7 +72,42 @@ def parse():
     p.add_argument("--probe-table-gb", type=float, default=32.0, help="gather-ceiling table size (>> 256 MiB Infinity Cache)")
     p.add_argument("--no-uniform-leg", action="store_true", help="skip the uniform-id (no locality) headline leg")
     p.add_argument("--dist-timeout", type=int, default=300, help="seconds before a stuck collective raises (N > 1)")
+    p.add_argument("--full", action="store_true", help="also run every leg beside the headline (peak probes, uniform-id "
+                                                       "leg, CPU baselines, cfg1-cfg5 extras, feature pipe, training steps); "
+                                                       "the --no-* options and --cpu-seconds 0 drop single legs of it")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed step computed to DIR/<name>.npy (float32)")
     return p.parse_args()
+
+
+def headline_only(args):
+    """A run without --full measures the headline alone: set-up, warm-up, the timed steps, the result line. Every other
+    leg is switched off here, whatever --no-* options were given (main() reads these flags; the tools that call one
+    leg's function with parse()'s defaults are not affected)."""
+    for flag in ("no_extras", "no_sharded", "no_train", "no_shard_train", "no_cascade", "no_pipe", "no_probes",
+                 "no_uniform_leg"):
+        setattr(args, flag, True)
+    args.cascade_sharded = False
+    args.cpu_seconds = 0.0
+    args.sim_ranks = 0
+
+
+DUMP_BYTES_MAX = 64 * 1000 * 1000
+
+
+def dump_outputs(path, out):
+    """--dump-outputs: the pooled [batch, slots * 2 * dim] fp32 matrix the last timed step wrote, as path/pooled.npy.
+    Past DUMP_BYTES_MAX a fixed sample of its rows (seeded, ascending; the same rows every run) is written instead."""
+    import numpy as np
+    import torch
+
+    os.makedirs(path, exist_ok=True)
+    rows = out.shape[0]
+    keep = max(1, DUMP_BYTES_MAX // (out.shape[1] * 4))
+    if keep < rows:
+        idx = np.sort(np.random.default_rng(20231).choice(rows, keep, replace=False))
+        out = out[torch.from_numpy(idx).to(out.device)]
+    np.save(os.path.join(path, "pooled.npy"), out.float().cpu().numpy())
 
 
 def launch(args) -> int:
@@ -116,6 +158,10 @@ def dry_run(args, world, rank):
 
 def main():
     args = parse()
+    if args.steps < 1:
+        raise SystemExit("bench.py: --steps must be at least 1")
+    if not args.full:
+        headline_only(args)
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(launch(args))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -182,6 +228,8 @@ def main():
             torch.cuda.synchronize()
             torch.cuda.empty_cache()
             probes = {"error": f"{type(e).__name__}: {e}"[:300]}
+    elif not args.full:
+        settle_clock()  # the headline starts from the loaded clock, as it does after the probes
     args.probes = probes
     torch.cuda.synchronize()
 
@@ -213,6 +261,8 @@ def main():
     bytes_per_launch_pad = sum(algo_bytes_pad[i % len(algo_bytes_pad)] for i in range(args.steps)) / args.steps
     achieved = bytes_per_launch / avg_kern_s / 1e9
     n_tok = sum(h.n_tokens for h in host) / len(host)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out)  # before any other leg reuses the buffer
 
     uniform_leg = None
     if not args.no_uniform_leg and not args.uniform:
@@ -350,6 +400,27 @@ def main():
             dist.destroy_process_group()
         except Exception:  # noqa: BLE001 — a communicator aborted by a failed leg
             pass
+
+
+def settle_clock(seconds: float = 0.3):
+    """About `seconds` of unrelated, untimed GPU work (rf_stream_copy over 1 GiB, past the Infinity Cache) before the
+    headline's warm-up when the peak probes do not run: tools/settle_probe.py measured that 0.3 s of any load brings
+    the clock to its settled value, which is the state the probes leave behind in a --full run."""
+    import torch
+
+    from recommendflow_amd.runtime import lib as L
+
+    n = 1 << 30
+    src = torch.empty(n, dtype=torch.uint8, device="cuda")
+    dst = torch.empty_like(src)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    while time.perf_counter() - t0 < seconds:
+        for _ in range(8):
+            L.call("rf_stream_copy", L.ptr(src), L.ptr(dst), n, 0, L.stream_ptr())
+        torch.cuda.synchronize()
+    del src, dst
+    torch.cuda.empty_cache()
 
 
 def _warm(fn, warm_s: float = 0.25, min_iters: int = 2):

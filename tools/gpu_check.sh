@@ -15,13 +15,14 @@ fi
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1
 rc=$?; echo "smoke rc=$rc"; tail -5 "$OUT/smoke.log"
 if [ $rc -ne 0 ]; then exit $rc; fi
-timeout -k 10 600 python bench.py ${BENCH_ARGS:-} > "$OUT/bench.log" 2>&1
+timeout -k 10 600 python bench.py --full ${BENCH_ARGS:-} > "$OUT/bench.log" 2>&1
 rc=$?; echo "bench rc=$rc"; tail -3 "$OUT/bench.log"
 if [ $rc -ne 0 ]; then exit $rc; fi
 if [ "${SKIP_PROF:-0}" != 1 ]; then
+  ROOT=$(pwd)
   cd /tmp && export TMPDIR=/tmp
-  timeout -k 10 600 rocprofv3 --kernel-trace --stats -d "$GRAFT_REPO_ROOT/$OUT/prof" -o run --output-format csv -- \
-      python3 "$GRAFT_REPO_ROOT/bench.py" ${PROF_ARGS:---cpu-seconds 0} > "$GRAFT_REPO_ROOT/$OUT/prof.log" 2>&1
-  rc=$?; echo "rocprof rc=$rc"; tail -3 "$GRAFT_REPO_ROOT/$OUT/prof.log"
-  find "$GRAFT_REPO_ROOT/$OUT/prof" -name "*stats*" | head
+  timeout -k 10 600 rocprofv3 --kernel-trace --stats -d "$ROOT/$OUT/prof" -o run --output-format csv -- \
+      python3 "$ROOT/bench.py" --full ${PROF_ARGS:---cpu-seconds 0} > "$ROOT/$OUT/prof.log" 2>&1
+  rc=$?; echo "rocprof rc=$rc"; tail -3 "$ROOT/$OUT/prof.log"
+  find "$ROOT/$OUT/prof" -name "*stats*" | head
 fi

@@ -11,7 +11,7 @@ while read -r group; do
   [ -z "$group" ] && continue
   n=$((n+1))
   timeout -k 10 300 rocprofv3 --kernel-trace --pmc $group -d "$OUT/pmc_$n" -o run --output-format csv -- \
-     python3 "$ROOT/bench.py" --steps 5 --warmup 1 --cpu-seconds 0 ${BENCH_ARGS:-} > "$OUT/pmc_$n.log" 2>&1
+     python3 "$ROOT/bench.py" --full --steps 5 --warmup 1 --cpu-seconds 0 ${BENCH_ARGS:-} > "$OUT/pmc_$n.log" 2>&1
   rc=$?; echo "pmc pass $n ($group) rc=$rc"
   if [ $rc -ne 0 ]; then tail -5 "$OUT/pmc_$n.log"; exit $rc; fi
 done <<LIST
