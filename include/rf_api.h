@@ -823,6 +823,44 @@ int rf_ip_candidates_bf16(const void* q, int64_t ldq, int32_t M, const void* ite
 int rf_ip_rescore_f32(const float* q, int64_t ldq, int32_t M, const float* items, int32_t K, const int32_t* count,
                       int32_t cap, float* cand_val, const uint32_t* cand_idx, int32_t order, void* stream);
 
+/* ---- recall search: IVF-Flat (FaissSearcher "IVF{nlist},Flat"; rf_ivf.hip) -------------------- */
+/*
+ * Inverted lists from one list id per item: a stable counting sort of the item indices 0 .. n-1 by assign[i].
+ * list_off[0 .. nlist] = exclusive prefix of the list sizes (list_off[nlist] = n), list_ids[list_off[l] ..
+ * list_off[l + 1]) = the items of list l, ascending. No result depends on the arrival order of atomics: two launches
+ * give identical arrays. 0 <= n < 2^31, 1 <= nlist <= 32768; assign values outside [0, nlist) are the caller's error
+ * (such items are dropped, the arrays are then not a partition). ws: rf_ivf_build_ws_bytes(n, nlist) bytes.
+ */
+size_t rf_ivf_build_ws_bytes(int64_t n, int32_t nlist);
+int rf_ivf_build_lists(const int32_t* assign, int64_t n, int32_t nlist, int32_t* list_off, uint32_t* list_ids, void* ws,
+                       size_t ws_bytes, void* stream);
+/*
+ * k-means centroid update: centroids[l] (F32 [nlist][K], in/out) = the mean of rows_sorted[list_off[l] ..
+ * list_off[l + 1]) (F32, contiguous rows of K, in list order), summed in a fixed order (chunks of 32 rows in row
+ * order, the chunks in a fixed order): the same bits on every launch. normalize = 1 divides the mean by its l2 norm
+ * (a zero norm leaves the mean). An empty list keeps its centroid. 1 <= K <= 1024, 1 <= nlist <= 32768.
+ */
+int rf_ivf_list_mean(const float* rows_sorted, int32_t K, const int32_t* list_off, int32_t nlist, int32_t normalize,
+                     float* centroids, void* stream);
+/*
+ * The IVF list scan. q: F32 [M][K] (row stride ldq); items_sorted: F32 [N][K], the item rows in list order (row r is
+ * item list_ids[r]); the (query, probed list) pairs come grouped by list: group g is list grp_list[g] with the pairs
+ * grp_off[g] .. grp_off[g + 1]; pair p is query pair_q[p] (in [0, M)) with start column pair_col[p]. For each pair
+ * (m, l, c) and every j < len(l) = list_off[l + 1] - list_off[l]:
+ *   cand_val[m][c + j] = <q_m, items_sorted[list_off[l] + j]>,  cand_idx[m][c + j] = list_ids[list_off[l] + j]
+ * (row stride ld; the caller keeps a query's column ranges disjoint and inside ld). Nothing else is written: with
+ * cand_val pre-filled with NaN the unwritten columns are never selected by rf_topk_merge_idx. Scores are fp32
+ * products with fp32 accumulation (v_mfma_f32_16x16x4_f32), k ascending: a score depends only on its query row, its
+ * item row and K, not on the other queries, the grouping or the launch (no bit parity with rf_linear_fwd; integer
+ * inputs with sums below 2^24 are exact). List-major: a list's rows are read once per 16 queries that probe it
+ * (once per list from HBM when K <= 256). K % 4 == 0, 4 <= K <= 1024, ldq % 4 == 0, q and items_sorted 16-byte
+ * aligned, M >= 1, N < 2^31, G <= 65535; empty lists and empty groups are allowed.
+ */
+int rf_ivf_scan_f32(const float* q, int64_t ldq, int32_t M, const float* items_sorted, int64_t N, int32_t K,
+                    const int32_t* list_off, const uint32_t* list_ids, const int32_t* grp_list, const int32_t* grp_off,
+                    int32_t G, const int32_t* pair_q, const int32_t* pair_col, float* cand_val, uint32_t* cand_idx,
+                    int64_t ld, void* stream);
+
 /*
  * Que2Search AttentionFusion forward (backend/layers/fusion_layers.py:35-46), fp32:
  * x: [batch][channels * dim] (the K.concatenate of the channel inputs, row stride ldx); W: [channels*dim][channels]

@@ -16,6 +16,9 @@ models/preranking/cold.py = prerank — an empty file, models/ranking = ESIM) gl
 
 Row gathers use rf_gather_rows (fp16 rows are moved as 2-byte elements). Everything stays on the GPU;
 the only host traffic is the final [B, K3] ids and scores.
+
+The recall index stays "Flat" (Cascade and ShardedCascade): an "IVF{nlist},Flat" result holds -1 ids where the
+probed lists have fewer than K1 items, and the prerank gather would index out of bounds with them.
 """
 from __future__ import annotations
 

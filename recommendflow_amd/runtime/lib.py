@@ -141,6 +141,11 @@ _SIGS = {
     "rf_ip_candidates_f32": (ctypes.c_int, [_vp, _i64, _i32, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _i64, _vp]),
     "rf_ip_rescore_f32": (ctypes.c_int, [_vp, _i64, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _i32, _vp]),
     "rf_ip_candidates_bf16": (ctypes.c_int, [_vp, _i64, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _i64, _vp]),
+    "rf_ivf_build_ws_bytes": (ctypes.c_size_t, [_i64, _i32]),
+    "rf_ivf_build_lists": (ctypes.c_int, [_vp, _i64, _i32, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
+    "rf_ivf_list_mean": (ctypes.c_int, [_vp, _i32, _vp, _i32, _i32, _vp, _vp]),
+    "rf_ivf_scan_f32": (ctypes.c_int, [_vp, _i64, _i32, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _i64,
+                                       _vp]),
 }
 EXPORTED = tuple(_SIGS)
 # include/rf_diag.h: tools-only entry points (not the production ABI)
