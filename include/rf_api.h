@@ -869,6 +869,23 @@ int rf_ivf_scan_f32(const float* q, int64_t ldq, int32_t M, const float* items_s
  */
 int rf_attention_fusion_fwd(const float* x, int32_t batch, int32_t channels, int32_t dim, int64_t ldx, const float* W,
                             int32_t is_norm, float* out, int64_t ldo, float* att_out, void* stream);
+/*
+ * AttentionFusion backward, fp32, same limits as the forward (1 <= channels <= 16, dim >= 1, batch 0 is a no-op).
+ * att: the forward's att_out [batch][channels]; dout: the gradient of out [batch][dim] (row stride ldg). Per example
+ * u = sum_c att_c x_c and ss = |u|^2 are recomputed; g_u = dout when !is_norm, else with r = rsqrt(max(ss, 1e-12))
+ * g_u = r dout - r^3 (u . dout) u when ss >= 1e-12 and r dout otherwise (the clamped branch of tf.nn.l2_normalize);
+ * s_c = g_u . x_c, dl_c = att_c (s_c - sum_c' att_c' s_c') (the softmax backward), and
+ *   dx[b][c dim + j] = att_c g_u[j] + sum_c' dl_c' W[c dim + j][c']      [batch][channels * dim], row stride lddx
+ *   dW[k][c]         = sum_b x[b][k] dl[b][c]                            [channels * dim][channels], overwritten
+ * dW may be NULL (skipped). dW is deterministic: the batch is cut into chunks that depend on batch
+ * alone, each chunk's partial lands in ws and the chunks are summed in order (no floating-point atomics): the same bits
+ * on every launch. ws: rf_attention_fusion_bwd_ws_bytes(batch, channels, dim) bytes, 16-byte aligned (g_u, dl and
+ * the chunk partials; needed with dW = NULL too).
+ */
+size_t rf_attention_fusion_bwd_ws_bytes(int32_t batch, int32_t channels, int32_t dim);
+int rf_attention_fusion_bwd(const float* x, int32_t batch, int32_t channels, int32_t dim, int64_t ldx, const float* W,
+                            int32_t is_norm, const float* att, const float* dout, int64_t ldg, float* dx, int64_t lddx,
+                            float* dW, void* ws, size_t ws_bytes, void* stream);
 
 /*
  * Measurement probes (not a reference operator: the ceilings SURVEY §8d states the hot path against).

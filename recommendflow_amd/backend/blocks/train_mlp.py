@@ -399,3 +399,50 @@ class TrainTower(torch.nn.Module):
             _linear_f32(h, Wf, bf, L.ACT["selu"], y, st)
             h = y
         return h
+
+
+class _LinearFn(torch.autograd.Function):
+    """y = x W^T + b and its three backward products on rf_gemm_f32 (through _gemm_layer: the supported_gemm guard
+    and the counted torch fallback for layouts the library refuses, e.g. a batch that is no multiple of 4 as the
+    weight gradient's contraction length)."""
+
+    @staticmethod
+    def forward(ctx, x, W, b):
+        st = L.stream_ptr(None)
+        y = torch.empty((x.shape[0], W.shape[0]), dtype=torch.float32, device=x.device)
+        _gemm_layer([(x, W, b, "none", y)], False, True, st)
+        ctx.save_for_backward(x, W)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, W = ctx.saved_tensors
+        st = L.stream_ptr(None)
+        dy = dy.float()
+        if dy.dim() != 2 or dy.stride(1) != 1:
+            dy = dy.contiguous()
+        dx = _gemm_layer([(dy, W, None, "none", None)], False, False, st)[0] if ctx.needs_input_grad[0] else None
+        dW = _gemm_layer([(dy, x, None, "none", None)], True, False, st)[0] if ctx.needs_input_grad[1] else None
+        db = dy.sum(dim=0) if ctx.needs_input_grad[2] else None
+        return dx, dW, db
+
+
+class TrainLinear(torch.nn.Module):
+    """Keras Dense(units, activation="linear") under training: glorot_uniform kernel (stored [units][in]), zero bias,
+    fp32, forward and backward on librf.so."""
+
+    def __init__(self, in_features: int, units: int, seed: int = 0, generator: Optional[torch.Generator] = None,
+                 device="cuda"):
+        super().__init__()
+        L.load()
+        L.require_gpu()
+        g = generator if generator is not None else torch.Generator().manual_seed(seed)
+        lim = math.sqrt(6.0 / (in_features + units))
+        self.W = torch.nn.Parameter(((torch.rand(units, in_features, generator=g) * 2 - 1) * lim).to(device))
+        self.b = torch.nn.Parameter(torch.zeros(units, device=device))
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        x = x.float()
+        if x.stride(1) != 1:
+            x = x.contiguous()
+        return _LinearFn.apply(x, self.W, self.b)

@@ -160,6 +160,10 @@ def gemm_f32_layer(problems, trans_a: bool = False, trans_b: bool = False, strea
         N = b.shape[0] if trans_b else b.shape[1]
         shapes.append((M, N))
     if group_pays(shapes):
-        return gemm_f32_grouped(problems, trans_a=trans_a, trans_b=trans_b, stream=stream)
+        # rf_gemm_f32_grouped takes 1..4 problems: more towers (the Que2Search channels) go in launches of 4
+        outs = []
+        for i in range(0, len(problems), 4):
+            outs += gemm_f32_grouped(problems[i: i + 4], trans_a=trans_a, trans_b=trans_b, stream=stream)
+        return outs
     return [gemm_f32(a, b, trans_a=trans_a, trans_b=trans_b, bias=bias, act=act, out=out, stream=stream)
             for a, b, bias, act, out in problems]

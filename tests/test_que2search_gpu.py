@@ -1,0 +1,154 @@
+"""GPU: TrainableQue2Search (1 user slot + 4 ad slots, D 8, dim 16, a 6000-row table) against the float64 restatement
+(tests/fusion_ref.py) composed from the model's own parameters and the GPU's own embed output. Tolerance per tensor
+as in test_fusion_train_gpu: err <= 8 x the float32-CPU restatement's err, floor 2^-20."""
+import numpy as np
+import pytest
+import torch
+
+import fusion_ref as R
+from recommendflow_amd.backend.encoder.sparse_encoder import FusedSparseEncoder, SlotSpec
+from recommendflow_amd.models.matching.que2search import TrainableQue2Search
+from recommendflow_amd.runtime import gemm as GM
+from recommendflow_amd.runtime.batch import synthetic_batch
+
+pytestmark = pytest.mark.gpu
+
+S, N_USER, D, DIM = 5, 1, 8, 16
+TRAIN_SEED = 3  # test_thirty_steps: chosen after checking that the float64 restatement's loss also falls on the batch
+
+
+def _model(dropout=0.0, loss="cosent", seed=1, enc_seed=4, lr=0.01):
+    specs = [SlotSpec(f"f{s}", 600, (2022, 2023), ["sum", "avg"][s % 2]) for s in range(S)]
+    enc = FusedSparseEncoder(specs, D, seed=enc_seed)
+    return TrainableQue2Search(enc, N_USER, DIM, dropout=dropout, loss=loss, learning_rate=lr, seed=seed)
+
+
+def _batch(B, seed=3):
+    return synthetic_batch(B, [s % 2 == 1 for s in range(S)], seed=seed, id_max=400, uniform=True).to("cuda")
+
+
+def _labels(B):
+    return (torch.arange(B, device="cuda") % 2).float()
+
+
+def _check(name, got, want64, want32, scale=None):
+    err, bar = R.rel_err(got, want64, scale), R.bar(want32, want64, scale)
+    print(f"{name}: err {err:.3e} bar {bar:.3e} (float32 CPU err {R.rel_err(want32, want64, scale):.3e})")
+    assert bool(torch.isfinite(got).all()) and err <= bar, (name, err, bar)
+
+
+def test_eval_forward(cuda):
+    model = _model()
+    hb = _batch(64)
+    model.step(hb, _labels(64))  # moving statistics and parameters away from their initial values
+    model.eval()
+    out = model(hb)
+    assert set(out) == {"query", "app"} and out["query"].shape == (64, DIM) and out["app"].shape == (64, DIM)
+    x = model.enc(hb).detach().cpu()
+    ref = {}
+    for dt in (torch.float64, torch.float32):
+        with torch.no_grad():
+            ref[dt] = R.que2search(model, R.model_params(model, dt), x.to(dt), training=False)
+    _check("eval query", out["query"], ref[torch.float64][0], ref[torch.float32][0])
+    _check("eval app", out["app"], ref[torch.float64][1], ref[torch.float32][1])
+
+
+def _restated_step(model, x, y, dtype, loss):
+    P = R.model_params(model, dtype)
+    xr = x.to(dtype).requires_grad_(True)
+    q, a = R.que2search(model, P, xr, training=True)
+    a.retain_grad()
+    lv = (R.cosent if loss == "cosent" else R.inbatch_ce)(y.cpu().to(dtype), q, a)
+    lv.backward()
+    return lv.detach(), {n: p.grad for n, p in P.items()}, xr.grad, a.grad
+
+
+@pytest.mark.parametrize("B,loss", [(64, "cosent"), (63, "cosent"), (64, "inbatch_ce")])
+def test_training_step_against_float64(cuda, B, loss):
+    """dropout = 0: the loss, every dense parameter's gradient and the gradient reaching the embed output. B = 63
+    is no multiple of 4, so the weight-gradient GEMMs (contraction over the batch) take the counted torch fallback."""
+    model = _model(loss=loss)
+    hb, y = _batch(B), _labels(B)
+    if loss == "inbatch_ce":
+        y = torch.ones(B, device="cuda")
+    x = model.enc(hb).detach().cpu()
+    seen = {}
+    fb0 = GM.torch_fallbacks
+    model.train()
+    q, a = model(hb, embed_hook=lambda gr: seen.setdefault("g", gr.detach().clone()))
+    lv = model.loss_fn(y, q, a)
+    lv.backward()
+    torch.cuda.synchronize()
+    if B % 4 == 0:
+        assert GM.torch_fallbacks == fb0, "a supported GEMM left librf"
+    else:
+        assert GM.torch_fallbacks > fb0
+    assert model.enc.grad is not None and model.enc.grad.count() > 0
+    l64, g64, dx64, da64 = _restated_step(model, x, y, torch.float64, loss)
+    l32, g32, dx32, _ = _restated_step(model, x, y, torch.float32, loss)
+    _check(f"loss B{B} {loss}", lv.detach().reshape(1), l64.reshape(1), l32.reshape(1))
+    named = dict(model.named_parameters())
+    assert set(named) == set(g64)
+    for n, p in named.items():
+        assert p.grad is not None, n
+        # in-batch softmax: a shift of every a_j by the same vector moves row i's logits by one constant, so the
+        # gradient of app_dense.b = sum_j dL/da_j is identically zero and max|want| is float64 rounding noise; err is
+        # then taken against the size of the rows that cancel, sum_j |dL/da_j| (same 8x rule and floor)
+        scale = float(da64.abs().sum(dim=0).max()) if (loss == "inbatch_ce" and n == "app_dense.b") else None
+        _check(f"grad {n} B{B} {loss}", p.grad, g64[n], g32[n], scale)
+    _check(f"grad embed output B{B} {loss}", seen["g"], dx64, dx32)
+
+
+def _run_steps(n, seed):
+    model = _model(dropout=0.3, seed=seed)
+    hb, y = _batch(64, seed=8), _labels(64)
+    plan = model.enc.backward_plan(hb)
+    rows = plan.rows[: int(plan.n_uniq)].long().clone()
+    t0 = model.embedding_table().clone()
+    losses = [model.step(hb, y).cpu().numpy().view(np.uint32).item() for _ in range(n)]
+    return model, losses, rows, t0
+
+
+def test_thirty_steps(cuda):
+    model, bits, rows, t0 = _run_steps(30, TRAIN_SEED)
+    losses = np.array(bits, np.uint32).view(np.float32)
+    print("losses", losses.tolist())
+    assert np.isfinite(losses).all()
+    assert losses[-1] < losses[0]
+    t1 = model.embedding_table()
+    assert rows.numel() > 0 and bool((t1[rows] != t0[rows]).any(dim=1).all()), "a touched table row did not move"
+    assert model.sparse_opt.iterations == 30 and model.dense_opt.iterations == 30
+    _, bits2, _, _ = _run_steps(30, TRAIN_SEED)
+    assert bits == bits2, "equal seeds gave different runs"
+
+
+def test_checkpoint_round_trip(cuda):
+    hb, y = _batch(64, seed=8), _labels(64)
+    a = _model(dropout=0.3, seed=TRAIN_SEED)
+    for _ in range(3):
+        a.step(hb, y)
+    sd = {k: v.detach().clone() for k, v in a.state_dict().items()}
+    b = _model(dropout=0.3, seed=TRAIN_SEED, enc_seed=9)  # another table: everything must come from the checkpoint
+    assert not torch.equal(a.enc.table, b.enc.table)
+    b.load_state_dict(sd)
+    la, lb = a.step(hb, y), b.step(hb, y)
+    assert la.cpu().numpy().view(np.uint32).item() == lb.cpu().numpy().view(np.uint32).item()
+    assert torch.equal(a.embedding_table(), b.embedding_table())
+    for p, q in zip(a.parameters(), b.parameters()):
+        assert torch.equal(p, q)
+
+
+def test_fusion_weights_sum_to_one(cuda):
+    model = _model()
+    model.eval()
+    model(_batch(64))
+    model(_batch(32, seed=5))
+    w = model.get_fusion_weights()
+    assert w["query"].shape == (1, N_USER) and w["app"].shape == (1, S - N_USER)
+    assert abs(float(w["query"].sum()) - 1.0) < 1e-6 and abs(float(w["app"].sum()) - 1.0) < 1e-6
+
+
+def test_step_refuses_data_parallel(cuda):
+    model = _model()
+    with pytest.raises(NotImplementedError):
+        model.step(_batch(8), _labels(8), dp=object())
