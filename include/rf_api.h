@@ -47,7 +47,9 @@ extern "C" {
 #define RF_COMB_MIN 3
 #define RF_COMB_FIRST 4 /* position 0 of each example (deviation D-first-last; `cls` aliases it) */
 #define RF_COMB_LAST 5  /* position Lmax-1 of each example (deviation D-first-last) */
-#define RF_COMB_NULL 6  /* no pooling: [Lmax, D] per table, concatenated along the sequence axis */
+#define RF_COMB_NULL 6  /* no pooling: [Lmax, D] per table, concatenated along the sequence axis. With
+                           RF_FLAG_MASK_PADDING a bag of len <= Lmax tokens is packed by its own length instead:
+                           table 0's len rows, then table 1's, then zeros up to 2 * Lmax rows */
 
 /* flags for rf_fused_hash_embed_fwd */
 #define RF_FLAG_MASK_PADDING 0x1 /* exclude padding positions (mask_zero intent); default OFF = reference parity:

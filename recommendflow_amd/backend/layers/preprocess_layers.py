@@ -140,7 +140,9 @@ class DoubleHashingEmbedding(torch.nn.Module):
 
     The two [num_bins, D] tables are two segments of one table (rows [base, base+N) and [base+N, base+2N));
     ``table``/``row_base`` let get_preprocess_layers place them inside a tower's fused table.
-    forward(one-slot SparseBatch | padded dense rows) -> [B, 2D]  (null: [B, 2*Lmax, D]).
+    forward(one-slot SparseBatch | padded dense rows) -> [B, 2D]  (null: [B, 2*Lmax, D]: table 0's Lmax positions, then
+    table 1's; with mask_padding a bag of len tokens is packed by its own length, table 0's len rows, table 1's len
+    rows, then zeros, as the oracle lays it out).
     """
 
     def __init__(self, num_bins, output_dim, seeds, combiner, mask_value=None, mask_zero=False, name="",

@@ -18,8 +18,9 @@ namespace rf {
 #ifndef RF_FUSED_WAVES
 #define RF_FUSED_WAVES 4
 #endif
-// waves per workgroup: items are wave-independent, and one-wave workgroups release their slots as soon
-// as their own item is done (a 4-wave workgroup holds its slots until the slowest of 4 items ends)
+// (items are wave-independent: the waves of a workgroup share nothing but its LDS allocation and never meet at
+// a workgroup barrier; a workgroup's slots are held until the slowest of its waves runs out of items, which the
+// grid-stride item loop keeps short)
 constexpr int kWaves = RF_FUSED_WAVES;
 constexpr int kCap = 768;    // tokens per wave item kept in the LDS row bucket (more: hashed inline)
 constexpr int kUnits = 64;   // examples per wave item (one slot per item)
@@ -118,9 +119,13 @@ __device__ __forceinline__ void add_pk(float* a, const float* f) {
 // fused multi-slot hash -> gather -> pool
 // ---------------------------------------------------------------------------------------------
 // row r (already clamped into the table), 16-byte chunk c: no bounds branch on the hot path
+// (the row's byte offset is one 32 x 32 -> 64 bit multiply of two unsigned values: a signed 64-bit `r * dim` took
+// two to four v_mad_u64_u32 per address)
 template <typename TT>
 __device__ __forceinline__ uint4 row_chunk(const TT* __restrict__ table, uint32_t r, int dim, int c) {
-    return *reinterpret_cast<const uint4*>(table + (int64_t)r * dim + (int64_t)c * Elem<TT>::EPV);
+    const uint32_t row_bytes = (uint32_t)dim * (uint32_t)sizeof(TT);
+    return *reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(table) + (uint32_t)c * 16u +
+                                           (uint64_t)r * row_bytes);
 }
 
 // PRE (rf_pool_rows_fwd): a row id with bit 31 set is row (r & 0x7fffffff) of the caller's LOCAL table
@@ -146,15 +151,23 @@ __device__ __forceinline__ uint4 row_chunk_src(const TT* __restrict__ table, con
 //      tables into the LDS bucket (indices never touch HBM);
 //  2.  the wave splits into TEAMS of LPR lanes (one 16-byte chunk per lane per row, CPL chunks);
 //      team t takes the units whose first token falls in the t-th share of the item's tokens and
-//      streams them through a two-stage software pipeline, accumulating in position order
+//      streams them through an NS-stage software pipeline (NS - 1 stages of row loads in flight while one
+//      is pooled; null, which stores every position, keeps two), accumulating in position order
 //      l = 0 .. L-1 with one fp32 add per position (bit-exact with the oracle); padded positions
 //      reuse the item's prefetched pad rows. Loads carry no branches: rows are clamped into the
 //      table in phase 1, and a slot whose descriptor does not fit the table is written as NaN.
-#ifndef RF_FUSED_MIN_WAVES
-#define RF_FUSED_MIN_WAVES 1
+// Waves per SIMD the register allocation is held to. One chunk per lane per row (CPL = 1, the cfg2 headline's
+// dim 64): 3, i.e. 168 VGPRs, what the kernel ran at before its pooling pipeline kept a stage in flight; uncapped
+// the allocator takes 186 and the kernel drops to 2 waves. Capped, it keeps 5 to 12 item-level registers in scratch
+// (stored once per launch, reloaded once per item, outside every gather loop). Wider rows hold 2 or 4 chunks per
+// lane per token and stay uncapped.
+#ifdef RF_FUSED_MIN_WAVES
+constexpr int fused_min_waves(int) { return RF_FUSED_MIN_WAVES; }  // A/B build option
+#else
+constexpr int fused_min_waves(int cpl) { return cpl == 1 ? 3 : 1; }
 #endif
 template <int LPR, int CPL, bool FULL, typename TT, typename OT, bool PRE>
-__global__ __launch_bounds__(kWaves * 64, RF_FUSED_MIN_WAVES) void fused_hash_embed_kernel(
+__global__ __launch_bounds__(kWaves * 64, fused_min_waves(CPL)) void fused_hash_embed_kernel(
     const rf_slot_desc* __restrict__ slots, int n_slots, const uint8_t* __restrict__ tok_bytes,
     const int32_t* __restrict__ tok_off, const int32_t* __restrict__ bag_off, const int32_t* __restrict__ lmax,
     int64_t n_units, const TT* __restrict__ table, int64_t table_rows, int dim, OT* __restrict__ out,
@@ -164,8 +177,12 @@ __global__ __launch_bounds__(kWaves * 64, RF_FUSED_MIN_WAVES) void fused_hash_em
 #ifdef RF_TOKENS_IN_FLIGHT
     constexpr int C = RF_TOKENS_IN_FLIGHT;
 #else
-    constexpr int C = CPL >= 2 ? 1 : 2;  // tokens per pipeline stage per team (2 stages in flight)
+    constexpr int C = CPL >= 2 ? 1 : 2;  // tokens per pipeline stage per team
 #endif
+    // pipeline stages per team, NS - 1 in flight while one is pooled. Same-box A/B on the cfg2 headline with the waits
+    // counted (profiles/r07/headline_pipe_ab.txt): 2 stages 0.2134 ms, 3 stages 0.2148, 4 stages 0.2248 (spills)
+    constexpr int NS = 2;
+    static_assert(NS >= 2, "the pooling pipeline needs a stage in flight");
     __shared__ uint32_t s_row[kWaves][2][kCap];
     __shared__ int32_t s_loc[kWaves][kUnits + 1];
     __shared__ int32_t s_gbeg[kWaves][kUnits];
@@ -317,15 +334,11 @@ __global__ __launch_bounds__(kWaves * 64, RF_FUSED_MIN_WAVES) void fused_hash_em
         if (lean) {
             constexpr int UPT = kUnits / TEAMS;     // bags per team
 #ifdef RF_LEAN_GU
-            constexpr int GU = RF_LEAN_GU;
+            constexpr int GU0 = RF_LEAN_GU;
 #else
-            constexpr int GU = CPL >= 2 ? 2 : 4;    // bags per load group
+            constexpr int GU0 = CPL >= 2 ? 2 : 4;   // bags per load group
 #endif
-#ifdef RF_LEAN_PIPE
-            constexpr bool LPIPE = RF_LEAN_PIPE != 0;  // A/B build option: group q0 + GU's loads issued before q0 is consumed
-#else
-            constexpr bool LPIPE = false;
-#endif
+            constexpr int GU = GU0 < UPT ? GU0 : UPT;
             // the element rule is wave-uniform per item: resolved once here, not as a chain of uniform branches
             // per element (as the single-token kernel)
             auto lean_body = [&](auto rule) __attribute__((always_inline)) {
@@ -344,11 +357,13 @@ __global__ __launch_bounds__(kWaves * 64, RF_FUSED_MIN_WAVES) void fused_hash_em
                         }
                     }
                 };
-                auto lean_consume = [&](const uint4 (&v)[GU][2][CPL], const bool (&has)[GU], int q0) __attribute__((always_inline)) {
+                // whole: the item holds all kUnits bags (wave-uniform), so no store sits under a per-bag branch
+                auto lean_consume = [&](const uint4 (&v)[GU][2][CPL], const bool (&has)[GU], int q0, auto whole)
+                                        __attribute__((always_inline)) {
 #pragma unroll
                     for (int g = 0; g < GU; ++g) {
                         const int j = team + TEAMS * (q0 + g);
-                        if (j >= nu) continue;
+                        if (q0 + g >= UPT || (!decltype(whole)::value && j >= nu)) continue;
                         const int64_t ob = (int64_t)(b0 + j) * out_stride + out_off;
                         const bool zero = !has[g] && mask_pad;
 #pragma unroll
@@ -367,25 +382,36 @@ __global__ __launch_bounds__(kWaves * 64, RF_FUSED_MIN_WAVES) void fused_hash_em
                             }
                     }
                 };
-                if constexpr (LPIPE) {
-                    uint4 va[GU][2][CPL], vb[GU][2][CPL];
-                    bool ha[GU], hb[GU];
-                    lean_issue(va, ha, 0);
-#pragma unroll 1
-                    for (int q0 = 0; q0 < UPT; q0 += 2 * GU) {
-                        if (q0 + GU < UPT) lean_issue(vb, hb, q0 + GU);
-                        lean_consume(va, ha, q0);
-                        if (q0 + GU >= UPT) break;
-                        if (q0 + 2 * GU < UPT) lean_issue(va, ha, q0 + 2 * GU);
-                        lean_consume(vb, hb, q0 + GU);
+                // Unrolled over the item's load groups, group g + 1's row loads issued BEFORE group g's stores, so
+                // the wait before group g's values leaves group g + 1's loads in flight (loads and stores retire in
+                // issue order on one counter; the rolled one-buffer loop drained it at every header). A whole item
+                // (wave-uniform) has no per-bag branch around its stores, which would put the waits under it.
+                auto lean_groups = [&](auto whole) __attribute__((always_inline)) {
+                    constexpr int NG = (UPT + GU - 1) / GU;
+                    uint4 v[2][GU][2][CPL];
+                    bool has[2][GU];
+                    lean_issue(v[0], has[0], 0);
+#pragma unroll
+                    for (int g = 0; g < NG; ++g) {
+                        if (g + 1 < NG) lean_issue(v[(g + 1) & 1], has[(g + 1) & 1], (g + 1) * GU);
+                        // (the table and the output do not alias, so the scheduler would lift every later group's
+                        //  loads up here too and size the register file for all of them)
+                        __builtin_amdgcn_sched_barrier(0);
+                        lean_consume(v[g & 1], has[g & 1], g * GU, whole);
+                        __builtin_amdgcn_sched_barrier(0);
                     }
+                };
+                // fp32 output only: with bf16 output (a rounding sequence per stored element) the unrolled form took
+                // the bf16-output units' compile from 4 to over 10 minutes; they keep the rolled one-buffer loop
+                if constexpr (sizeof(OT) == 4) {
+                    if (nu == kUnits) lean_groups(std::true_type{}); else lean_groups(std::false_type{});
                 } else {
 #pragma unroll 1
                     for (int q0 = 0; q0 < UPT; q0 += GU) {
                         uint4 v[GU][2][CPL];
                         bool has[GU];
                         lean_issue(v, has, q0);
-                        lean_consume(v, has, q0);
+                        lean_consume(v, has, q0, std::false_type{});
                     }
                 }
             };
@@ -424,7 +450,9 @@ __global__ __launch_bounds__(kWaves * 64, RF_FUSED_MIN_WAVES) void fused_hash_em
             ubeg = s_loc[wave][j];
             uend = s_loc[wave][j + 1];
             const int ul = uend - ubeg;
-            Lu = comb == RF_COMB_NULL ? lm : ((mask_pad || abl_nopad) ? ul : max(lm, ul));
+            // null keeps every position: Lmax of them, or with masked padding the bag's own (the oracle's layout:
+            // both tables' rows packed at the front of the slot's 2 * Lmax positions, zeros behind them)
+            Lu = comb == RF_COMB_NULL ? (mask_pad ? min(ul, lm) : lm) : ((mask_pad || abl_nopad) ? ul : max(lm, ul));
             obase = (int64_t)(b0 + j) * out_stride + out_off;
 #pragma unroll
             for (int k = 0; k < 2; ++k)
@@ -439,10 +467,19 @@ __global__ __launch_bounds__(kWaves * 64, RF_FUSED_MIN_WAVES) void fused_hash_em
             for (int e = 0; e < EPV; ++e) g[e] = ok ? f[e] : __builtin_nanf("");
             store_chunk<OT, EPV>(out + off, g);
         };
-        auto finish_unit = [&]() {
+        // kind: the item's combiner when the caller has resolved it (the pipelined loop; sum stands for sum and
+        // avg), so only that combiner's code is inlined at every unit close; any_comb = decided here
+        using any_comb = std::integral_constant<int, -1>;
+        const int comb_item = comb;
+        auto finish_unit = [&](auto kind) {
+            constexpr int K = decltype(kind)::value;
+            const int comb = K < 0 ? comb_item
+                                   : K == RF_COMB_SUM ? (comb_item == RF_COMB_AVG ? RF_COMB_AVG : RF_COMB_SUM) : K;
             const int ul = uend - ubeg;
             const int npad = Lu - ul;
             if (comb == RF_COMB_NULL) {
+                // (masked padding: Lu = the bag's length, no pad position; the zeros behind the rows are written after
+                //  the team's last unit)
                 for (int p = ul; p < Lu; ++p)
 #pragma unroll
                     for (int k = 0; k < 2; ++k)
@@ -451,10 +488,6 @@ __global__ __launch_bounds__(kWaves * 64, RF_FUSED_MIN_WAVES) void fused_hash_em
                             if (!cown[cc]) continue;
                             float f[EPV];
                             unpack16<TT>(padv[k][cc], f);
-                            if (mask_pad) {
-#pragma unroll
-                                for (int e = 0; e < EPV; ++e) f[e] = 0.0f;
-                            }
                             put(obase + ((int64_t)k * Lu + p) * dim + cidx[cc] * EPV, f);
                         }
                 return;
@@ -545,9 +578,15 @@ __global__ __launch_bounds__(kWaves * 64, RF_FUSED_MIN_WAVES) void fused_hash_em
         };
 
         if (ja < jb) {
-            start_unit();
             const int tb0 = s_loc[wave][ja], tb1 = s_loc[wave][jb];
             const int th = min(tb1, kCap);  // hot range: rows staged in LDS
+            // rows of one chunk per lane (CPL = 1), sum / avg: the NS-stage pipeline; wider rows (2 or 4 loads per
+            // lane per row already) and the other combiners keep the two-stage loop
+            const bool piped = CPL == 1 && (comb == RF_COMB_SUM || comb == RF_COMB_AVG) && tb0 < th;
+            if (piped) {  // the pipeline opens units by their tokens: start at the unit that holds token tb0
+                while (s_loc[wave][j + 1] <= tb0) ++j;
+            }
+            start_unit();
             auto issue = [&](uint4 (&v)[C][2][CPL], int c0) {
 #pragma unroll
                 for (int q = 0; q < C; ++q) {
@@ -560,36 +599,100 @@ __global__ __launch_bounds__(kWaves * 64, RF_FUSED_MIN_WAVES) void fused_hash_em
                     }
                 }
             };
-            auto drain = [&](const uint4 (&v)[C][2][CPL], int c0) {
+            int jhot = ja;  // units ja .. jhot - 1 that hold no token are left to the pass after the last unit
+            if (piped) {
+                // NS stages of C tokens per team, NS - 1 of them in flight while one is pooled. The steady-state
+                // round is one path: stage s + NS - 1 is issued, then stage s is pooled with no branch around
+                // the use of its rows, so the wait before it counts exactly the younger
+                // stages' loads and leaves them in flight. A unit close (two stores per chunk) sits under a branch
+                // BEFORE that use; the stores it adds only make the counted wait reach a little into the next stage.
+                // Empty bags never enter: a token that leaves the open unit opens the unit that holds it.
+                using sum_kind = std::integral_constant<int, RF_COMB_SUM>;
+                {
+                    auto pool = [&](const uint4 (&w)[C][2][CPL], int c0, auto guard) __attribute__((always_inline)) {
+                        constexpr bool G = decltype(guard)::value;  // last round: tokens past the range are not pooled
 #pragma unroll
-                for (int q = 0; q < C; ++q) {
-                    const int i = c0 + q;
-                    if (i < th) {
-                        while (i >= uend) {  // close the current unit (and any empty ones after it)
-                            finish_unit();
-                            ++j;
-                            start_unit();
+                        for (int q = 0; q < C; ++q) {
+                            const int i = c0 + q;
+                            const bool live = !G || i < th;
+                            if (live && i >= uend) {
+                                finish_unit(sum_kind{});
+                                do ++j; while (s_loc[wave][j + 1] <= i);
+                                start_unit();
+                            }
+#pragma unroll
+                            for (int k = 0; k < 2; ++k)
+#pragma unroll
+                                for (int cc = 0; cc < CPL; ++cc) {
+                                    float f[EPV];
+                                    unpack16<TT>(w[q][k][cc], f);
+                                    float* a = acc[k][cc];
+                                    if constexpr (!G) {
+                                        add_pk<EPV>(a, f);
+                                    } else {
+                                        float t[EPV];
+#pragma unroll
+                                        for (int e = 0; e < EPV; ++e) t[e] = a[e];
+                                        add_pk<EPV>(t, f);
+#pragma unroll
+                                        for (int e = 0; e < EPV; ++e) a[e] = live ? t[e] : a[e];
+                                    }
+                                }
                         }
-                        consume(v[q], i - ubeg);
+                    };
+                    uint4 v[NS][C][2][CPL];
+                    int c0 = tb0;
+#pragma unroll
+                    for (int s = 0; s < NS - 1; ++s) {
+                        issue(v[s], c0 + s * C);
+                        // stage by stage, as the loop reissues them: an interleaved prologue would make the loop's
+                        // first wait cover the later stages' loads too (the wait must hold for both ways in)
+                        __builtin_amdgcn_sched_barrier(0);
                     }
+                    auto round = [&](auto guard) __attribute__((always_inline)) {
+#pragma unroll
+                        for (int s = 0; s < NS; ++s) {
+                            issue(v[(s + NS - 1) % NS], c0 + (s + NS - 1) * C);
+                            pool(v[s], c0 + s * C, guard);
+                        }
+                        c0 += NS * C;
+                    };
+                    while (c0 + NS * C <= th) round(std::false_type{});  // every token of the round is in range
+                    round(std::true_type{});  // fewer than NS * C tokens left (loads past the range re-read a row)
                 }
-            };
-            uint4 va[C][2][CPL], vb[C][2][CPL];
-            int c0 = tb0;
-            if (c0 < th) issue(va, c0);
-            while (c0 < th) {
-                if (c0 + C < th) issue(vb, c0 + C);
-                drain(va, c0);
-                c0 += C;
-                if (c0 >= th) break;
-                if (c0 + C < th) issue(va, c0 + C);
-                drain(vb, c0);
-                c0 += C;
+                jhot = j;
+            } else {
+                auto drain = [&](const uint4 (&v)[C][2][CPL], int c0) {
+#pragma unroll
+                    for (int q = 0; q < C; ++q) {
+                        const int i = c0 + q;
+                        if (i < th) {
+                            while (i >= uend) {  // close the current unit (and any empty ones after it)
+                                finish_unit(any_comb{});
+                                ++j;
+                                start_unit();
+                            }
+                            consume(v[q], i - ubeg);
+                        }
+                    }
+                };
+                uint4 va[C][2][CPL], vb[C][2][CPL];
+                int c0 = tb0;
+                if (c0 < th) issue(va, c0);
+                while (c0 < th) {
+                    if (c0 + C < th) issue(vb, c0 + C);
+                    drain(va, c0);
+                    c0 += C;
+                    if (c0 >= th) break;
+                    if (c0 + C < th) issue(va, c0 + C);
+                    drain(vb, c0);
+                    c0 += C;
+                }
             }
             // cold range (item holds more than kCap tokens): hash inline, one token at a time
             for (int i = max(tb0, kCap); i < tb1; ++i) {
                 while (i >= uend) {
-                    finish_unit();
+                    finish_unit(any_comb{});
                     ++j;
                     start_unit();
                 }
@@ -618,9 +721,30 @@ __global__ __launch_bounds__(kWaves * 64, RF_FUSED_MIN_WAVES) void fused_hash_em
                 consume(v, i - ubeg);
             }
             while (true) {
-                finish_unit();
+                finish_unit(any_comb{});
                 if (++j >= jb) break;
                 start_unit();
+            }
+            // bags without tokens that the pipeline stepped over
+            for (j = ja; j < jhot; ++j) {
+                if (s_loc[wave][j + 1] != s_loc[wave][j]) continue;
+                start_unit();
+                finish_unit(any_comb{});
+            }
+            // null with masked padding: positions 2 * len .. 2 * Lmax - 1 of every bag are zeros (one place, not at
+            // every unit close: inlined there it cost the whole kernel 8 more spilled registers)
+            if (comb == RF_COMB_NULL && mask_pad) {
+                float z[EPV];
+#pragma unroll
+                for (int e = 0; e < EPV; ++e) z[e] = 0.0f;
+                for (j = ja; j < jb; ++j) {
+                    const int l2 = 2 * min(s_loc[wave][j + 1] - s_loc[wave][j], lm);
+                    const int64_t ob = (int64_t)(b0 + j) * out_stride + out_off;
+                    for (int p = l2; p < 2 * lm; ++p)
+#pragma unroll
+                        for (int cc = 0; cc < CPL; ++cc)
+                            if (cown[cc]) put(ob + (int64_t)p * dim + cidx[cc] * EPV, z);
+                }
             }
         }
         wave_lds_sync();  // the LDS bucket is rewritten by the next item
