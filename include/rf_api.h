@@ -889,6 +889,57 @@ int rf_attention_fusion_bwd(const float* x, int32_t batch, int32_t channels, int
                             int32_t is_norm, const float* att, const float* dout, int64_t ldg, float* dx, int64_t lddx,
                             float* dW, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- Feature-interaction layers, forward (backend/layers/network_layers.py; rf_interact.hip) ------------ */
+/*
+ * Factorization machine, FM_Layer.call (network_layers.py:43-56) and New_FM.call (:193-207):
+ *   out[b] = (w0 ? *w0 : 0) + (w ? sum_{i<n} w[w_ids[b][i]] : 0) + 0.5 sum_d((sum_f e[b][f][d])^2 - sum_f e[b][f][d]^2)
+ * Exactly one of x and V is given. Dense (New_FM): e = x[b][f][d], x F32 or BF16, d contiguous, element strides
+ * x_stride_b and x_stride_f (the encoder's [B, S*2D] output is a [B, S, 2D] view with x_stride_f = 2D). Gathered
+ * (FM_Layer): e[b][f] = V[ids[b][f]], V F32 [v_rows][dim], ids int64 [batch][fields] (row stride ld_ids); [B, fields,
+ * dim] is never written. First order: w F32 [w_rows] (the [feature_length, 1] weight), w_ids int64 [batch][n] (row
+ * stride ld_wids); w = NULL skips it, w0 = NULL is 0. An id outside its table reads as NaN, as an out-of-range row of
+ * rf_embedding_bag_fwd does (so out[b] is NaN; tf.nn.embedding_lookup raises on the CPU and returns zeros on the GPU).
+ * fp32 arithmetic, the field sum sequential in f, the sums over d and n in a fixed tree: the same bits on every launch.
+ * out: F32 [batch]. Limits: 1 <= dim <= 1024, 1 <= fields <= 4096, 0 <= n <= 4096.
+ */
+int rf_fm_fwd(const void* x, int32_t x_dtype, int64_t x_stride_b, int64_t x_stride_f, const float* V, const int64_t* ids,
+              int64_t ld_ids, int64_t v_rows, int32_t batch, int32_t fields, int32_t dim, const float* w0, const float* w,
+              const int64_t* w_ids, int32_t n, int64_t ld_wids, int64_t w_rows, float* out, void* stream);
+/*
+ * Cross network, CrossNetwork.call (network_layers.py:163-171), all layers in one launch:
+ *   x_{l+1}[b] = x_0[b] (x_l[b] . w_l) + b_l + x_l[b]        l < n_layers;  out[b] = x_{n_layers}[b]
+ * x: F32 or BF16 [batch][dim] (row stride ldx), read once; w, b: F32 [n_layers][dim] (the reference's (dim, 1) weights
+ * of a layer as one row); out: F32 [batch][dim] (row stride ldo), written once. A row stays in registers through the
+ * layers (256 threads up to dim 4096, 1024 threads above). fp32, fixed reduction order. Limits: 1 <= n_layers <= 16,
+ * 1 <= dim <= 32768.
+ */
+int rf_cross_fwd(const void* x, int32_t x_dtype, int64_t ldx, int32_t batch, int32_t dim, int32_t n_layers, const float* w,
+                 const float* b, float* out, int64_t ldo, void* stream);
+/*
+ * Compressed interaction network, CIN.call (network_layers.py:238-255). With X^0 = x[b] ([fields][dim]), H_0 = fields
+ * and sizes = [H_1 .. H_K] (a HOST array):
+ *   X^{k+1}[h][d] = sum_{i<fields} sum_{j<H_k} W_k[i H_k + j][h] X^0[i][d] X^k[j][d]      k = 0 .. K-1
+ *   out[b] = concat_k(sum_d X^{k+1}[:][d])                                               F32 [batch][sum(sizes)], stride ldo
+ * (the field of X^0 major in the flattened index, as the reshape at :246 gives; no activation, no split-half; the
+ * reference docstring's "(None, dim)" is wrong). x: F32 or BF16, d contiguous, element strides x_stride_b, x_stride_f.
+ * Precision: each product X^0[i][d] X^k[j][d] is formed in fp32 and rounded once (RNE) to bf16; W is bf16; the sums
+ * over (i, j) are fp32 accumulators of v_mfma_f32_16x16x32_bf16; X^{k+1} is carried between the layers in fp32; the
+ * sum over d is fp32 in a fixed order. The outer products are generated in registers as the MFMA A operand; nothing of
+ * size [batch][dim][fields H_k] is written. No divisibility requirement: fields, H_k and dim are padded with zeros
+ * inside the kernel.
+ * rf_cin_pack_w writes layer `layer` of the bf16 kernel image from its fp32 master W ([fields * H_layer][H_{layer+1}],
+ * the Keras filter (1, fields H_k, H_{k+1})) into packed (rf_cin_packed_w_bytes bytes, 16-byte aligned, all layers).
+ * ws: rf_cin_ws_bytes bytes, 16-byte aligned (the per-16-rows sums, added per example in order).
+ * Limits: fields <= 512, sizes[k] <= 512, dim <= 256, 1 <= n_layers <= 8.
+ */
+size_t rf_cin_packed_w_bytes(int32_t fields, const int32_t* sizes, int32_t n_layers);
+size_t rf_cin_ws_bytes(int32_t batch, int32_t fields, int32_t dim, const int32_t* sizes, int32_t n_layers);
+int rf_cin_pack_w(const float* W, int32_t layer, int32_t fields, const int32_t* sizes, int32_t n_layers, void* packed,
+                  void* stream);
+int rf_cin_fwd(const void* x, int32_t x_dtype, int64_t x_stride_b, int64_t x_stride_f, int32_t batch, int32_t fields,
+               int32_t dim, const int32_t* sizes, int32_t n_layers, const void* packed_w, float* out, int64_t ldo, void* ws,
+               size_t ws_bytes, void* stream);
+
 /*
  * Measurement probes (not a reference operator: the ceilings SURVEY §8d states the hot path against).
  * rf_stream_copy: dst = src, n_bytes % 16 == 0, 16-byte aligned; float4 STREAM copy (2 * n_bytes of HBM traffic);

@@ -1,4 +1,4 @@
-"""Attention helpers (reference: backend/layers/layer_utils.py)."""
+"""Attention helpers and index_mapping (reference: backend/layers/layer_utils.py)."""
 from __future__ import annotations
 
 from typing import Optional
@@ -37,3 +37,14 @@ def scaled_dot_product_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tens
 def split_heads(x: torch.Tensor, seq_len: int, num_heads: int, depth: int) -> torch.Tensor:
     """[B, L, H*depth] -> [B, H, L, depth] (layer_utils.py:27-38); a view-level helper."""
     return x.reshape(-1, seq_len, num_heads, depth).permute(0, 2, 1, 3)
+
+
+def index_mapping(inputs_dict: dict, map_dict: dict) -> dict:
+    """Feature index mapping (layer_utils.py:41-53): {'I1': ids, ...} + {'I1': 0, 'I2': 100, ...} ->
+    {'I1': (ids + offset) reshaped to [-1, 1], ...}. An input key without an offset raises ValueError."""
+    outputs_dict = {}
+    for key, value in inputs_dict.items():
+        if map_dict.get(key) is None:
+            raise ValueError("map dict error!")
+        outputs_dict[key] = (torch.as_tensor(value) + map_dict[key]).reshape(-1, 1)
+    return outputs_dict

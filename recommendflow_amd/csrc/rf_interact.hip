@@ -1,0 +1,563 @@
+// rf_interact.hip — feature-interaction layers of the non-attention rankers (backend/layers/network_layers.py), forward:
+//   rf_fm_fwd     FM_Layer.call :43-56 and New_FM.call :193-207 (DeepFM): first order + 0.5 sum_d((sum_f e)^2 - sum_f e^2)
+//   rf_cross_fwd  CrossNetwork.call :163-171 (DCN): x_{l+1} = x_0 (x_l . w_l) + b_l + x_l, every layer in one launch
+//   rf_cin_fwd    CIN.call :238-255 (xDeepFM): per layer a GEMM whose A operand (the outer products X0[i,d] X^k[j,d]) is
+//                 generated in registers and never written to HBM
+// All three are deterministic: no floating-point atomics, every reduction in a fixed order.
+//
+// FM: one wave per example. A lane owns the columns d = lane, lane + 64, ...; the field sum is sequential in f (eight
+// row loads in flight, compensated: the two sums cancel), the column sum and the first-order sum are xor-shuffle
+// trees. fp32 throughout.
+//
+// Cross: one block per row, the row (x_0 and x_l) in registers for all layers: 256 threads x up to 16 elements for
+// dim <= 4096, 1024 threads x up to 32 elements above. x is read once and out is written once; w_l and b_l come from
+// L2. The dot product is summed per thread in element order, then by the shuffle tree, then over the waves in order.
+//
+// CIN: rows of the GEMMs are (example, d) pairs, an example's d padded to 16-row subtiles (D <= 256: at most 16), so
+// that a subtile belongs to one example. A workgroup of 4 waves owns MS subtiles (MS = 4, 2, 1: the largest whose LDS
+// fits) and runs every layer on them: X0 and X^k stay in LDS as fp32 [row][h + pad], pitch = 4 mod 8 floats, which
+// makes the 32-byte row reads of the A fragment conflict-free. For v_mfma_f32_16x16x32_bf16 lane l holds A[row l & 15]
+// [k = 8 (l >> 4) + e]; with H_k padded to a multiple of 8 a lane's eight k are one field i of X0 and eight consecutive
+// j of X^k, so a fragment is one X0 value times eight X^k values, each product formed in fp32 and rounded once (RNE,
+// v_cvt_pk_bf16_f32). The fragment is reused for every 16-column tile of the layer's output that the wave owns. W_k is
+// read as a packed bf16 image (rf_cin_pack_w) [k step of 32][16-column tile][lane][8], so a wave's B fragment is one
+// conflict-free 16-byte LDS read and a stage of the image is a flat copy; two stages sit in LDS and two more are in
+// flight in registers, with one barrier per stage. The accumulators are fp32; X^{k+1} goes back to LDS in fp32, its sum over the subtile's
+// 16 rows goes to the workspace, and a second kernel adds an example's subtiles in order.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+
+#include "rf_common.h"
+
+namespace {
+
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+template <typename T>
+__device__ __forceinline__ float ld_f32(const T* p);
+template <>
+__device__ __forceinline__ float ld_f32<float>(const float* p) { return *p; }
+template <>
+__device__ __forceinline__ float ld_f32<uint16_t>(const uint16_t* p) { return bf16_bits_to_f32(*p); }
+
+// ---------------------------------------------------------------------------------------------------------------
+// FM
+// ---------------------------------------------------------------------------------------------------------------
+constexpr int kFmMaxDim = 1024, kFmMaxFields = 4096;
+
+// sum += v with the rounding error carried in c (Kahan): the field sums cancel in (sum e)^2 - sum e^2, and plain
+// sequential fp32 sums of a few hundred fields leave 1e-6 of the result
+__device__ __forceinline__ void kahan_add(float& sum, float& c, float v) {
+    const float y = v - c;
+    const float t = sum + y;
+    c = (t - sum) - y;
+    sum = t;
+}
+
+// GATHER: e[b][f] = V[ids[b][f]] (a row outside [0, v_rows) reads as NaN, as rf_embedding_bag_fwd's rows do)
+template <typename T, bool GATHER>
+__global__ __launch_bounds__(256) void fm_kernel(const T* __restrict__ x, int64_t sb, int64_t sf,
+                                                 const int64_t* __restrict__ ids, int64_t ld_ids, int64_t v_rows, int B,
+                                                 int fields, int dim, const float* __restrict__ w0,
+                                                 const float* __restrict__ w, const int64_t* __restrict__ w_ids, int n,
+                                                 int64_t ld_wids, int64_t w_rows, float* __restrict__ out) {
+    const int lane = threadIdx.x & 63;
+    const int64_t b = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (b >= B) return;
+    const int64_t* idr = GATHER ? ids + b * ld_ids : nullptr;
+    const T* xb = GATHER ? x : x + b * sb;
+    auto row = [&](int f) -> const T* {
+        if (!GATHER) return xb + (int64_t)f * sf;
+        const int64_t r = idr[f];
+        return r < 0 || r >= v_rows ? nullptr : xb + r * (int64_t)dim;
+    };
+    float second = 0.f;
+    for (int d = lane; d < dim; d += 64) {
+        float s = 0.f, q = 0.f, cs = 0.f, cq = 0.f;  // cs, cq: the running compensations of s and q
+        int f = 0;
+        for (; f + 8 <= fields; f += 8) {
+            float e[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                const T* r = row(f + u);
+                e[u] = r ? ld_f32(r + d) : __uint_as_float(0x7fc00000u);
+            }
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                kahan_add(s, cs, e[u]);
+                kahan_add(q, cq, e[u] * e[u]);
+            }
+        }
+        for (; f < fields; ++f) {
+            const T* r = row(f);
+            const float e = r ? ld_f32(r + d) : __uint_as_float(0x7fc00000u);
+            kahan_add(s, cs, e);
+            kahan_add(q, cq, e * e);
+        }
+        second += s * s - q;
+    }
+    second = wave_sum(second);
+    float first = 0.f;
+    if (w) {
+        const int64_t* wr = w_ids + b * ld_wids;
+        for (int i = lane; i < n; i += 64) {
+            const int64_t r = wr[i];
+            first += r < 0 || r >= w_rows ? __uint_as_float(0x7fc00000u) : w[r];
+        }
+        first = wave_sum(first);
+    }
+    if (lane == 0) out[b] = ((w0 ? *w0 : 0.f) + first) + 0.5f * second;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Cross
+// ---------------------------------------------------------------------------------------------------------------
+constexpr int kCrossMaxLayers = 16, kCrossMaxDim = 32768;
+
+template <typename T, int THREADS, int EPT>
+__global__ __launch_bounds__(THREADS) void cross_kernel(const T* __restrict__ x, int64_t ldx, int dim, int L,
+                                                        const float* __restrict__ w, const float* __restrict__ bias,
+                                                        float* __restrict__ out, int64_t ldo) {
+    constexpr int NW = THREADS / 64;
+    __shared__ float red[2][NW];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const T* xr = x + (int64_t)blockIdx.x * ldx;
+    const int ne = tid < dim ? (dim - tid + THREADS - 1) / THREADS : 0;  // this thread's elements: e < ne
+    float x0[EPT], xl[EPT];
+#pragma unroll
+    for (int e = 0; e < EPT; ++e) {
+        x0[e] = e < ne ? ld_f32(xr + tid + e * THREADS) : 0.f;
+        xl[e] = x0[e];
+    }
+    for (int l = 0; l < L; ++l) {
+        const float* wl = w + (int64_t)l * dim;
+        const float* bl = bias + (int64_t)l * dim;
+        float dot = 0.f;
+#pragma unroll
+        for (int e = 0; e < EPT; ++e) {
+            dot += xl[e] * (e < ne ? wl[tid + e * THREADS] : 0.f);
+            if (e % 8 == 7) __builtin_amdgcn_sched_barrier(0);  // at most eight w loads in flight: no spills at EPT = 32
+        }
+        dot = wave_sum(dot);
+        if (lane == 0) red[l & 1][wave] = dot;  // two buffers: one barrier per layer is enough
+        __syncthreads();
+        float s = red[l & 1][0];
+#pragma unroll
+        for (int v = 1; v < NW; ++v) s += red[l & 1][v];
+#pragma unroll
+        for (int e = 0; e < EPT; ++e) {
+            xl[e] = (x0[e] * s + (e < ne ? bl[tid + e * THREADS] : 0.f)) + xl[e];
+            if (e % 8 == 7) __builtin_amdgcn_sched_barrier(0);
+        }
+    }
+    float* o = out + (int64_t)blockIdx.x * ldo;
+#pragma unroll
+    for (int e = 0; e < EPT; ++e) {
+        if (e < ne) o[tid + e * THREADS] = xl[e];
+    }
+}
+
+template <typename T, int THREADS, int EPT>
+void launch_cross(const void* x, int64_t ldx, int B, int dim, int L, const float* w, const float* b, float* out,
+                  int64_t ldo, hipStream_t st) {
+    hipLaunchKernelGGL((cross_kernel<T, THREADS, EPT>), dim3(B), dim3(THREADS), 0, st, (const T*)x, ldx, dim, L, w, b, out,
+                       ldo);
+}
+
+template <typename T>
+void dispatch_cross(const void* x, int64_t ldx, int B, int dim, int L, const float* w, const float* b, float* out,
+                    int64_t ldo, hipStream_t st) {
+#define RF_CROSS(TH, E) launch_cross<T, TH, E>(x, ldx, B, dim, L, w, b, out, ldo, st)
+    if (dim <= 256) RF_CROSS(256, 1);
+    else if (dim <= 512) RF_CROSS(256, 2);
+    else if (dim <= 1024) RF_CROSS(256, 4);
+    else if (dim <= 2048) RF_CROSS(256, 8);
+    else if (dim <= 4096) RF_CROSS(256, 16);
+    else if (dim <= 8192) RF_CROSS(1024, 8);
+    else if (dim <= 16384) RF_CROSS(1024, 16);
+    else RF_CROSS(1024, 32);
+#undef RF_CROSS
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// CIN
+// ---------------------------------------------------------------------------------------------------------------
+constexpr int kCinMaxLayers = 8, kCinMaxF = 512, kCinMaxH = 512, kCinMaxD = 256;
+constexpr int kStageVec = 1024;  // uint4 per W stage (16 KiB): KST k steps x NTC tiles x 64 lanes
+
+inline int pad_to(int v, int m) { return (v + m - 1) / m * m; }
+
+struct CinPlan {
+    int K, F0, D, dsub;   // dsub: 16-row subtiles per example
+    int H[kCinMaxLayers + 1];   // H[0] = F0, H[k + 1] = sizes[k]
+    int Hp[kCinMaxLayers + 1];  // padded to 8: the k index of layer k is i * Hp[k] + j
+    int nks[kCinMaxLayers];     // k steps of 32
+    int nt[kCinMaxLayers];      // 16-column tiles of the layer's output
+    int ooff[kCinMaxLayers];    // first column of the layer in out
+    int64_t woff[kCinMaxLayers + 1];  // the layer's image in the packed buffer, in uint4
+    int sumH, pitch0, pitchX;
+};
+
+// sizes is a host array; returns false (and names the argument) on a limit
+bool cin_plan(int fields, int dim, const int32_t* sizes, int n_layers, CinPlan& p, const char* who) {
+    if (n_layers < 1 || n_layers > kCinMaxLayers) {
+        rf_set_error(RF_EINVAL, "%s: n_layers (%d) must be in [1, %d]", who, n_layers, kCinMaxLayers);
+        return false;
+    }
+    if (fields < 1 || fields > kCinMaxF) {
+        rf_set_error(RF_EINVAL, "%s: fields (%d) must be in [1, %d]", who, fields, kCinMaxF);
+        return false;
+    }
+    if (dim < 1 || dim > kCinMaxD) {
+        rf_set_error(RF_EINVAL, "%s: dim (%d) must be in [1, %d]", who, dim, kCinMaxD);
+        return false;
+    }
+    if (!sizes) {
+        rf_set_error(RF_EINVAL, "%s: sizes is null", who);
+        return false;
+    }
+    p.K = n_layers;
+    p.F0 = fields;
+    p.D = dim;
+    p.dsub = (dim + 15) / 16;
+    p.H[0] = fields;
+    p.Hp[0] = pad_to(fields, 8);
+    p.sumH = 0;
+    p.woff[0] = 0;
+    int hmax = 0;
+    for (int k = 0; k < n_layers; ++k) {
+        if (sizes[k] < 1 || sizes[k] > kCinMaxH) {
+            rf_set_error(RF_EINVAL, "%s: sizes[%d] (%d) must be in [1, %d]", who, k, sizes[k], kCinMaxH);
+            return false;
+        }
+        p.H[k + 1] = sizes[k];
+        p.Hp[k + 1] = pad_to(sizes[k], 8);
+        p.nks[k] = pad_to(fields * p.Hp[k], 32) / 32;
+        p.nt[k] = (sizes[k] + 15) / 16;
+        p.ooff[k] = p.sumH;
+        p.sumH += sizes[k];
+        p.woff[k + 1] = p.woff[k] + (int64_t)p.nks[k] * p.nt[k] * 64;
+        if (k + 1 < n_layers) hmax = std::max(hmax, sizes[k]);
+    }
+    p.pitch0 = p.Hp[0] + 4;
+    p.pitchX = pad_to(std::max(hmax, 1), 16) + 4;  // every computed column (tiles of 16) is stored
+    return true;
+}
+
+// LDS of a workgroup of MS subtiles: X0, the X^k ping-pong (none for one layer, one for two) and two W stages
+inline size_t cin_lds_bytes(const CinPlan& p, int ms) {
+    const int nbuf = p.K >= 3 ? 2 : p.K - 1;
+    return (size_t)ms * 16 * ((size_t)p.pitch0 + (size_t)nbuf * p.pitchX) * sizeof(float) + 2 * kStageVec * sizeof(uint4);
+}
+
+struct CinArgs {
+    const void* x;
+    int64_t sb, sf;
+    int64_t n_sub;  // batch * dsub
+    const uint4* wimg;
+    float* part;  // [n_sub][sumH]
+    CinPlan p;
+};
+
+// image of one layer: [k step][tile][lane][8 bf16]; element e of lane l of (ks, tile) is W[k = 32 ks + 8 (l >> 4) + e]
+// [n = 16 tile + (l & 15)] with k = i * Hp + j, zero where i, j or n is padding
+__global__ __launch_bounds__(256) void cin_pack_kernel(const float* __restrict__ W, int F0, int Hk, int Hp, int Hn, int nt,
+                                                       int64_t total, uint4* __restrict__ img) {
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= total) return;
+    const int lane = (int)(t & 63);
+    const int64_t kt = t >> 6;
+    const int tile = (int)(kt % nt);
+    const int64_t ks = kt / nt;
+    const int n = tile * 16 + (lane & 15);
+    const int64_t k0 = ks * 32 + 8 * (lane >> 4);
+    const int i = (int)(k0 / Hp), j0 = (int)(k0 % Hp);
+    uint32_t h[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        const int j = j0 + e;
+        const float v = i < F0 && j < Hk && n < Hn ? W[((int64_t)i * Hk + j) * Hn + n] : 0.f;
+        h[e] = f32_to_bf16_bits(v);
+    }
+    img[t] = make_uint4(h[0] | (h[1] << 16), h[2] | (h[3] << 16), h[4] | (h[5] << 16), h[6] | (h[7] << 16));
+}
+
+template <int MS, typename T>
+__global__ __launch_bounds__(256) void cin_kernel(const CinArgs a) {
+    constexpr int MT = MS * 16;           // rows of the workgroup
+    constexpr int NW = 4 / MS;            // waves side by side over the output columns
+    constexpr int TPW = MS == 1 ? 4 : 8;  // tiles per wave and pass
+    constexpr int NTC = NW * TPW;         // tiles per pass: 8, 16, 16
+    constexpr int KST = kStageVec / (NTC * 64);  // k steps per stage: 2, 1, 1
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const CinPlan& p = a.p;
+    float* x0s = reinterpret_cast<float*>(smem);
+    float* xs[2];
+    xs[0] = x0s + MT * p.pitch0;
+    xs[1] = xs[0] + MT * p.pitchX;
+    const int nbuf = p.K >= 3 ? 2 : p.K - 1;
+    uint4* wst = reinterpret_cast<uint4*>(x0s + MT * (p.pitch0 + nbuf * p.pitchX));
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wm = wave % MS, wn = wave / MS;
+    const int lr = lane & 15, lg = lane >> 4;
+    const int64_t u0 = (int64_t)blockIdx.x * MS;
+
+    // X0 -> LDS [row][i], zero in the padding (i >= F0, d >= D, subtiles past the batch)
+    {
+        const int m = tid % MT;
+        const int64_t u = u0 + m / 16;
+        const int64_t b = u / p.dsub;
+        const int d = (int)(u - b * p.dsub) * 16 + (m & 15);
+        const bool live = u < a.n_sub && d < p.D;
+        const T* xp = static_cast<const T*>(a.x) + b * a.sb + d;
+        for (int i = tid / MT; i < p.Hp[0]; i += 256 / MT)
+            x0s[m * p.pitch0 + i] = live && i < p.F0 ? ld_f32(xp + (int64_t)i * a.sf) : 0.f;
+    }
+    __syncthreads();
+
+    for (int k = 0; k < p.K; ++k) {
+        const float* src = k == 0 ? x0s : xs[(k - 1) & 1];
+        const int spitch = k == 0 ? p.pitch0 : p.pitchX;
+        float* dst = xs[k & 1];
+        const bool last = k + 1 == p.K;
+        const int Hp = p.Hp[k], F0 = p.F0, nks = p.nks[k], NT = p.nt[k], Hn = p.H[k + 1];
+        const int stepi = 32 / Hp, stepj = 32 % Hp;
+        const uint4* wl = a.wimg + p.woff[k];
+        const float* arow = src + (wm * 16 + lr) * spitch;
+        const float* x0row = x0s + (wm * 16 + lr) * p.pitch0;
+        const int nstage = (nks + KST - 1) / KST;
+
+        for (int c0 = 0; c0 < NT; c0 += NTC) {
+            const int ntc = min(NTC, NT - c0);
+            f32x4 acc[TPW];
+#pragma unroll
+            for (int t = 0; t < TPW; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+            int i = (8 * lg) / Hp, j = (8 * lg) % Hp;
+
+            // W stages: two in flight in registers (the stage after next is requested before this one is computed),
+            // two in LDS
+            uint4 pre[4], nxt[4];
+            auto prefetch = [&](int s, uint4(&dr)[4]) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const int q = tid + 256 * e;
+                    const int ks = q / (NTC * 64), r = q % (NTC * 64);
+                    const int kstep = s * KST + ks;
+                    dr[e] = kstep < nks && r < ntc * 64 ? wl[((int64_t)kstep * NT + c0) * 64 + r] : make_uint4(0, 0, 0, 0);
+                }
+            };
+            auto commit = [&](int buf) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) wst[buf * kStageVec + tid + 256 * e] = pre[e];
+            };
+            prefetch(0, pre);
+            commit(0);
+            __syncthreads();
+            if (nstage > 1) prefetch(1, pre);
+            for (int s = 0; s < nstage; ++s) {
+                if (s + 2 < nstage) prefetch(s + 2, nxt);
+                const uint4* wb = wst + (s & 1) * kStageVec;
+#pragma unroll
+                for (int ks = 0; ks < KST; ++ks) {
+                    {
+                        // no branch on the k step or the tile: past the layer's k steps and past the pass's tiles the
+                        // stage holds zeros, and a branch here makes the compiler shuffle the accumulators.
+                        // the A fragment: X0[i] times X^k[j .. j + 7], fp32 products rounded once to bf16
+                        const float x0v = i < F0 ? x0row[i] : 0.f;
+                        const float4 v0 = *reinterpret_cast<const float4*>(arow + j);
+                        const float4 v1 = *reinterpret_cast<const float4*>(arow + j + 4);
+                        bf16x8 af;
+                        af[0] = (__bf16)(x0v * v0.x);
+                        af[1] = (__bf16)(x0v * v0.y);
+                        af[2] = (__bf16)(x0v * v0.z);
+                        af[3] = (__bf16)(x0v * v0.w);
+                        af[4] = (__bf16)(x0v * v1.x);
+                        af[5] = (__bf16)(x0v * v1.y);
+                        af[6] = (__bf16)(x0v * v1.z);
+                        af[7] = (__bf16)(x0v * v1.w);
+#pragma unroll
+                        for (int t = 0; t < TPW; ++t) {
+                            const int tl = wn + NW * t;  // tile of this pass
+                            const bf16x8 bfr = __builtin_bit_cast(bf16x8, wb[(ks * NTC + tl) * 64 + lane]);
+                            acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, bfr, acc[t], 0, 0, 0);
+                        }
+                        i += stepi;
+                        j += stepj;
+                        if (j >= Hp) {
+                            j -= Hp;
+                            ++i;
+                        }
+                    }
+                }
+                if (s + 1 < nstage) commit((s + 1) & 1);
+                __syncthreads();
+#pragma unroll
+                for (int e = 0; e < 4; ++e) pre[e] = nxt[e];
+            }
+            // C: column lr, rows 4 lg + r. X^{k+1} -> LDS (all 16 columns of a tile: the padding is exactly zero),
+            // the subtile's row sum -> the workspace
+            const int64_t u = u0 + wm;
+#pragma unroll
+            for (int t = 0; t < TPW; ++t) {
+                const int tl = wn + NW * t;
+                if (tl < ntc) {
+                    const int col = (c0 + tl) * 16 + lr;
+                    if (!last) {
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) dst[(wm * 16 + 4 * lg + r) * p.pitchX + col] = acc[t][r];
+                    }
+                    float v = ((acc[t][0] + acc[t][1]) + acc[t][2]) + acc[t][3];
+                    v += __shfl_xor(v, 16, 64);
+                    v += __shfl_xor(v, 32, 64);
+                    if (lg == 0 && col < Hn && u < a.n_sub) a.part[u * p.sumH + p.ooff[k] + col] = v;
+                }
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// out[b][c] = the example's subtile sums added in subtile order
+__global__ __launch_bounds__(256) void cin_reduce_kernel(const float* __restrict__ part, int64_t total, int sumH, int dsub,
+                                                         float* __restrict__ out, int64_t ldo) {
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= total) return;
+    const int64_t b = t / sumH;
+    const int c = (int)(t - b * sumH);
+    const float* pr = part + b * dsub * (int64_t)sumH + c;
+    float s = 0.f;
+    for (int u = 0; u < dsub; ++u) s += pr[(int64_t)u * sumH];
+    out[b * ldo + c] = s;
+}
+
+template <int MS, typename T>
+int launch_cin(const CinArgs& a, size_t lds, hipStream_t st) {
+    auto kern = cin_kernel<MS, T>;
+    if (lds > 64 * 1024) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return rf_set_error(RF_EHIP, "rf_cin_fwd: hipFuncSetAttribute: %s", hipGetErrorString(e));
+    }
+    const int64_t grid = (a.n_sub + MS - 1) / MS;
+    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), lds, st, a);
+    return RF_OK;
+}
+
+}  // namespace
+
+extern "C" int rf_fm_fwd(const void* x, int32_t x_dtype, int64_t x_stride_b, int64_t x_stride_f, const float* V,
+                         const int64_t* ids, int64_t ld_ids, int64_t v_rows, int32_t batch, int32_t fields, int32_t dim,
+                         const float* w0, const float* w, const int64_t* w_ids, int32_t n, int64_t ld_wids, int64_t w_rows,
+                         float* out, void* stream) {
+    RF_REQUIRE(batch >= 0, "rf_fm_fwd: batch must be >= 0");
+    RF_REQUIRE(dim >= 1 && dim <= kFmMaxDim, "rf_fm_fwd: dim (%d) must be in [1, %d]", dim, kFmMaxDim);
+    RF_REQUIRE(fields >= 1 && fields <= kFmMaxFields, "rf_fm_fwd: fields (%d) must be in [1, %d]", fields, kFmMaxFields);
+    RF_REQUIRE(n >= 0 && n <= kFmMaxFields, "rf_fm_fwd: n (%d) must be in [0, %d]", n, kFmMaxFields);
+    RF_REQUIRE((x != nullptr) != (V != nullptr), "rf_fm_fwd: give exactly one of x (dense) and V (gathered)");
+    if (x) {
+        RF_REQUIRE(x_dtype == RF_DTYPE_F32 || x_dtype == RF_DTYPE_BF16, "rf_fm_fwd: x_dtype must be F32 or BF16");
+        RF_REQUIRE(x_stride_f >= dim && x_stride_b >= 0, "rf_fm_fwd: x_stride_f must be >= dim");
+    } else {
+        RF_REQUIRE(ids && ld_ids >= fields && v_rows >= 1, "rf_fm_fwd: the gathered form needs ids, ld_ids >= fields, v_rows >= 1");
+    }
+    RF_REQUIRE(!w || (w_ids && ld_wids >= n && w_rows >= 1), "rf_fm_fwd: w needs w_ids, ld_wids >= n, w_rows >= 1");
+    if (batch == 0) return RF_OK;
+    RF_REQUIRE(out, "rf_fm_fwd: out is null");
+    hipStream_t st = rf_stream(stream);
+    const dim3 grid((batch + 3) / 4), block(256);
+#define RF_FM(T, G, XP)                                                                                                    \
+    hipLaunchKernelGGL((fm_kernel<T, G>), grid, block, 0, st, (const T*)(XP), x_stride_b, x_stride_f, ids, ld_ids, v_rows, \
+                       batch, fields, dim, w0, w, w_ids, n, ld_wids, w_rows, out)
+    if (V) RF_FM(float, true, V);
+    else if (x_dtype == RF_DTYPE_F32) RF_FM(float, false, x);
+    else RF_FM(uint16_t, false, x);
+#undef RF_FM
+    return rf_check_launch("rf_fm_fwd");
+}
+
+extern "C" int rf_cross_fwd(const void* x, int32_t x_dtype, int64_t ldx, int32_t batch, int32_t dim, int32_t n_layers,
+                            const float* w, const float* b, float* out, int64_t ldo, void* stream) {
+    RF_REQUIRE(batch >= 0, "rf_cross_fwd: batch must be >= 0");
+    RF_REQUIRE(n_layers >= 1 && n_layers <= kCrossMaxLayers, "rf_cross_fwd: n_layers (%d) must be in [1, %d]", n_layers, kCrossMaxLayers);
+    RF_REQUIRE(dim >= 1 && dim <= kCrossMaxDim, "rf_cross_fwd: dim (%d) must be in [1, %d]", dim, kCrossMaxDim);
+    RF_REQUIRE(x_dtype == RF_DTYPE_F32 || x_dtype == RF_DTYPE_BF16, "rf_cross_fwd: x_dtype must be F32 or BF16");
+    RF_REQUIRE(ldx >= dim && ldo >= dim, "rf_cross_fwd: ldx and ldo must be >= dim");
+    if (batch == 0) return RF_OK;
+    RF_REQUIRE(x && w && b && out, "rf_cross_fwd: null pointer");
+    hipStream_t st = rf_stream(stream);
+    if (x_dtype == RF_DTYPE_F32) dispatch_cross<float>(x, ldx, batch, dim, n_layers, w, b, out, ldo, st);
+    else dispatch_cross<uint16_t>(x, ldx, batch, dim, n_layers, w, b, out, ldo, st);
+    return rf_check_launch("rf_cross_fwd");
+}
+
+extern "C" size_t rf_cin_packed_w_bytes(int32_t fields, const int32_t* sizes, int32_t n_layers) {
+    CinPlan p;
+    if (!cin_plan(fields, 1, sizes, n_layers, p, "rf_cin_packed_w_bytes")) return 0;
+    return (size_t)p.woff[n_layers] * sizeof(uint4);
+}
+
+extern "C" size_t rf_cin_ws_bytes(int32_t batch, int32_t fields, int32_t dim, const int32_t* sizes, int32_t n_layers) {
+    CinPlan p;
+    if (batch < 0 || !cin_plan(fields, dim, sizes, n_layers, p, "rf_cin_ws_bytes")) return 0;
+    return std::max<size_t>((size_t)batch * p.dsub * p.sumH * sizeof(float), 16);
+}
+
+extern "C" int rf_cin_pack_w(const float* W, int32_t layer, int32_t fields, const int32_t* sizes, int32_t n_layers,
+                             void* packed, void* stream) {
+    CinPlan p;
+    if (!cin_plan(fields, 1, sizes, n_layers, p, "rf_cin_pack_w")) return RF_EINVAL;
+    RF_REQUIRE(layer >= 0 && layer < n_layers, "rf_cin_pack_w: layer (%d) must be in [0, %d)", layer, n_layers);
+    RF_REQUIRE(W && packed && ((uintptr_t)packed & 15) == 0, "rf_cin_pack_w: null pointer or packed not 16-byte aligned");
+    const int64_t total = p.woff[layer + 1] - p.woff[layer];
+    hipLaunchKernelGGL(cin_pack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, rf_stream(stream), W, p.F0,
+                       p.H[layer], p.Hp[layer], p.H[layer + 1], p.nt[layer], total,
+                       static_cast<uint4*>(packed) + p.woff[layer]);
+    return rf_check_launch("rf_cin_pack_w");
+}
+
+extern "C" int rf_cin_fwd(const void* x, int32_t x_dtype, int64_t x_stride_b, int64_t x_stride_f, int32_t batch,
+                          int32_t fields, int32_t dim, const int32_t* sizes, int32_t n_layers, const void* packed_w,
+                          float* out, int64_t ldo, void* ws, size_t ws_bytes, void* stream) {
+    CinArgs a;
+    if (!cin_plan(fields, dim, sizes, n_layers, a.p, "rf_cin_fwd")) return RF_EINVAL;
+    RF_REQUIRE(batch >= 0, "rf_cin_fwd: batch must be >= 0");
+    RF_REQUIRE(x_dtype == RF_DTYPE_F32 || x_dtype == RF_DTYPE_BF16, "rf_cin_fwd: x_dtype must be F32 or BF16");
+    RF_REQUIRE(x_stride_f >= dim && x_stride_b >= 0, "rf_cin_fwd: x_stride_f must be >= dim");
+    RF_REQUIRE(ldo >= a.p.sumH, "rf_cin_fwd: ldo must be >= sum(sizes)");
+    if (batch == 0) return RF_OK;
+    RF_REQUIRE(x && packed_w && out, "rf_cin_fwd: null pointer");
+    RF_REQUIRE(((uintptr_t)packed_w & 15) == 0, "rf_cin_fwd: packed_w must be 16-byte aligned");
+    RF_REQUIRE(ws && ((uintptr_t)ws & 15) == 0, "rf_cin_fwd: null or misaligned workspace");
+    RF_REQUIRE(ws_bytes >= rf_cin_ws_bytes(batch, fields, dim, sizes, n_layers), "rf_cin_fwd: ws_bytes too small");
+    a.x = x;
+    a.sb = x_stride_b;
+    a.sf = x_stride_f;
+    a.n_sub = (int64_t)batch * a.p.dsub;
+    a.wimg = static_cast<const uint4*>(packed_w);
+    a.part = static_cast<float*>(ws);
+    RF_REQUIRE(a.n_sub < ((int64_t)1 << 31), "rf_cin_fwd: batch * dim too large");
+    hipStream_t st = rf_stream(stream);
+    int ms = 4;
+    while (ms > 1 && cin_lds_bytes(a.p, ms) > 160 * 1024) ms >>= 1;
+    const size_t lds = cin_lds_bytes(a.p, ms);
+    RF_REQUIRE(lds <= 160 * 1024, "rf_cin_fwd: needs %zu bytes of LDS (> 160 KiB)", lds);
+    const bool f32 = x_dtype == RF_DTYPE_F32;
+    int rc;
+    if (ms == 4) rc = f32 ? launch_cin<4, float>(a, lds, st) : launch_cin<4, uint16_t>(a, lds, st);
+    else if (ms == 2) rc = f32 ? launch_cin<2, float>(a, lds, st) : launch_cin<2, uint16_t>(a, lds, st);
+    else rc = f32 ? launch_cin<1, float>(a, lds, st) : launch_cin<1, uint16_t>(a, lds, st);
+    if (rc != RF_OK) return rc;
+    const int64_t total = (int64_t)batch * a.p.sumH;
+    hipLaunchKernelGGL(cin_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, a.part, total, a.p.sumH,
+                       a.p.dsub, out, ldo);
+    return rf_check_launch("rf_cin_fwd");
+}
