@@ -940,6 +940,40 @@ int rf_cin_fwd(const void* x, int32_t x_dtype, int64_t x_stride_b, int64_t x_str
                int32_t dim, const int32_t* sizes, int32_t n_layers, const void* packed_w, float* out, int64_t ldo, void* ws,
                size_t ws_bytes, void* stream);
 
+/* ---- Feature-interaction layers, backward of FM and CrossNetwork (rf_interact.hip) ----------------------- */
+/*
+ * Backward of the second-order term of rf_fm_fwd. With S[b][d] = sum_f e[b][f][d] and g = dout[b] (F32 [batch]):
+ *   dx[b][f][d] = g (S[b][d] - e[b][f][d])        F32, element strides dx_stride_b and dx_stride_f, written once
+ * x, x_dtype, x_stride_*, V, ids, ld_ids, v_rows, batch, fields, dim: as rf_fm_fwd (exactly one of x and V). Dense:
+ * dx is the gradient of x (the gradient of the encoder's [B, S*2D] output viewed as [B, S, 2D], in place). Gathered:
+ * dx holds the per-position gradient rows of V in (b, f) order; the caller sums them per id with
+ * rf_segment_sum_rows(ids, dx, batch * fields, ...), the order in which Keras deduplicates an IndexedSlices gradient
+ * (an id repeated inside an example needs no special case). An id outside the table makes S NaN as in the forward:
+ * every row of that example is NaN, and rf_segment_sum_rows drops the out-of-range id. The first-order gradients need
+ * no kernel: dw = rf_segment_sum_rows over w_ids of dout[b] repeated n times, dw0 = sum_b dout[b].
+ * fp32; S is summed sequentially in f with compensation (Kahan) and stays in registers; the same bits on every launch.
+ * Limits as the forward: 1 <= dim <= 1024, 1 <= fields <= 4096; dx_stride_f >= dim, dx_stride_b >= (fields - 1) *
+ * dx_stride_f + dim.
+ */
+int rf_fm_bwd(const void* x, int32_t x_dtype, int64_t x_stride_b, int64_t x_stride_f, const float* V, const int64_t* ids,
+              int64_t ld_ids, int64_t v_rows, int32_t batch, int32_t fields, int32_t dim, const float* dout, float* dx,
+              int64_t dx_stride_b, int64_t dx_stride_f, void* stream);
+/*
+ * Backward of rf_cross_fwd (s_l = x_l . w_l, x_{l+1} = x_0 s_l + b_l + x_l); activations are recomputed from x. With
+ * g_L = dout (F32 [batch][dim], row stride lddo), for l = L-1 .. 0:
+ *   ds_l = g_{l+1} . x_0,  db_l = sum_b g_{l+1},  dw_l = sum_b ds_l x_l,  g_l = g_{l+1} + w_l ds_l
+ *   dx = g_0 + sum_l s_l g_{l+1}
+ * dx: F32 [batch][dim] (row stride lddx), written once. dw, db: F32 [n_layers][dim], overwritten. The batch sums are
+ * taken over chunks of 128 examples in example order and the chunks are added in order: no floating-point atomics,
+ * no [batch][n_layers][dim] intermediate, the same bits on every launch. ws: rf_cross_bwd_ws_bytes bytes, 16-byte
+ * aligned (2 n_layers scalars per example and the chunk partials). Limits as the forward: 1 <= n_layers <= 16,
+ * 1 <= dim <= 32768, x F32 or BF16; batch 0 is a no-op.
+ */
+size_t rf_cross_bwd_ws_bytes(int32_t batch, int32_t dim, int32_t n_layers);
+int rf_cross_bwd(const void* x, int32_t x_dtype, int64_t ldx, int32_t batch, int32_t dim, int32_t n_layers, const float* w,
+                 const float* b, const float* dout, int64_t lddo, float* dx, int64_t lddx, float* dw, float* db, void* ws,
+                 size_t ws_bytes, void* stream);
+
 /*
  * Measurement probes (not a reference operator: the ceilings SURVEY §8d states the hot path against).
  * rf_stream_copy: dst = src, n_bytes % 16 == 0, 16-byte aligned; float4 STREAM copy (2 * n_bytes of HBM traffic);

@@ -1,12 +1,17 @@
-"""Feature-interaction layers (reference: backend/layers/network_layers.py), forward on rf_interact.hip:
+"""Feature-interaction layers (reference: backend/layers/network_layers.py) on rf_interact.hip:
 
   FM_Layer, New_FM  -> rf_fm_fwd     (:43-56, :193-207)
   CrossNetwork      -> rf_cross_fwd  (:163-171)
   CIN               -> rf_cin_fwd    (:238-255)
 
 Weights are created on the first call from the input shape, as Keras `build` does: 'random_normal' and
-tf.random_normal_initializer() are N(0, 0.05^2), w0 starts at zero. The regularisation coefficients are kept and have
-no effect on a forward. Inference only: the backward of these layers is not implemented.
+tf.random_normal_initializer() are N(0, 0.05^2), w0 starts at zero. FM_Layer, New_FM, CrossNetwork and CIN are the
+inference layers: their parameters do not require gradients and their regularisation coefficients have no effect.
+
+TrainFMLayer, TrainNewFM and TrainCrossNetwork are the same layers under training: the parameters require gradients,
+the forward joins torch autograd through rf_fm_fwd / rf_fm_bwd (the first-order and the gathered gradients reduced per
+id by rf_segment_sum_rows) and rf_cross_fwd / rf_cross_bwd, and regularization() is Keras' l2(c) penalty c * sum(w^2)
+of the weights (w_reg, v_reg, reg_w, reg_b), which a model adds to its loss. CIN has no backward.
 """
 from __future__ import annotations
 
@@ -231,3 +236,217 @@ class CIN(torch.nn.Module):
         L.call("rf_cin_fwd", L.ptr(x), L.torch_dtype_code(x.dtype), x.stride(0), x.stride(1), B, fields, dim, self._sizes, K,
                L.ptr(self._packed), L.ptr(out), out.stride(0), L.ptr(ws), ws.numel(), L.stream_ptr())
         return out
+
+
+# ---- training ----------------------------------------------------------------------------------------------------------
+def _segment_sum(ids: torch.Tensor, vals: torch.Tensor, id_range: int):
+    """rf_segment_sum_rows: ids int64 [n], vals f32 [n, D] (D a multiple of 4, at most 256) -> (distinct ids ascending,
+    their rows summed in input order); ids outside [0, id_range) are dropped. Reads the device count (one sync)."""
+    n, D = vals.shape
+    cap = max(1, min(n, id_range))
+    dev = vals.device
+    uid = torch.empty(cap, dtype=torch.int64, device=dev)
+    uval = torch.empty((cap, D), dtype=torch.float32, device=dev)
+    n_uniq = torch.zeros(1, dtype=torch.int32, device=dev)
+    wsb = int(L.load().rf_segment_sum_ws_bytes(n, id_range))
+    ws = torch.empty(max(wsb, 256), dtype=torch.uint8, device=dev)
+    L.call("rf_segment_sum_rows", L.ptr(ids), L.ptr(vals), n, D, id_range, L.ptr(uid), L.ptr(uval), cap, L.ptr(n_uniq),
+           L.ptr(ws), ws.numel(), L.stream_ptr())
+    k = int(n_uniq.item())
+    return uid[:k], uval[:k]
+
+
+def _dense_row_grad(ids: torch.Tensor, vals: torch.Tensor, rows: int, width: int) -> torch.Tensor:
+    """The dense [rows, width] gradient of a table from its per-position gradient rows vals [n, >= width] (columns past
+    `width` are padding to rf_segment_sum_rows' multiple of 4): per-id sums in position order, untouched rows zero."""
+    out = torch.zeros((rows, width), dtype=torch.float32, device=vals.device)
+    ids = ids.reshape(-1).contiguous()
+    for c0 in range(0, vals.shape[1], 256):
+        blk = vals[:, c0: c0 + 256]
+        if vals.shape[1] > 256:
+            blk = blk.contiguous()
+        uid, uval = _segment_sum(ids, blk, rows)
+        w = min(width - c0, blk.shape[1])
+        if w > 0:
+            out[uid, c0: c0 + w] = uval[:, :w]
+    return out
+
+
+def _first_order_grad(dout: torch.Tensor, w_ids: torch.Tensor, rows: int) -> torch.Tensor:
+    """dw [rows, 1]: dout[b] added to every id of example b, in (b, i) order."""
+    B, n = w_ids.shape
+    vals = torch.zeros((B * n, 4), dtype=torch.float32, device=dout.device)
+    vals[:, 0] = dout.repeat_interleave(n)
+    return _dense_row_grad(w_ids, vals, rows, 1)
+
+
+def _row_grad(dout: torch.Tensor) -> torch.Tensor:
+    return dout.float().reshape(-1).contiguous()
+
+
+class _FmDenseFn(torch.autograd.Function):
+    """New_FM: out = rf_fm_fwd(x, w[w_ids]); dx = rf_fm_bwd, dw = the per-id sums of dout."""
+
+    @staticmethod
+    def forward(ctx, x, w, w_ids):
+        ctx.save_for_backward(x, w_ids)
+        ctx.w_rows = None if w is None else w.shape[0]
+        return fm_forward(embed=x, w=w, w_ids=w_ids)
+
+    @staticmethod
+    def backward(ctx, dout):
+        x, w_ids = ctx.saved_tensors
+        g = _row_grad(dout)
+        dx = dw = None
+        if ctx.needs_input_grad[0]:
+            B, fields, dim = x.shape
+            dx = torch.empty((B, fields, dim), dtype=torch.float32, device=x.device)
+            L.call("rf_fm_bwd", L.ptr(x), L.torch_dtype_code(x.dtype), x.stride(0), x.stride(1), None, None, 0, 0, B, fields,
+                   dim, L.ptr(g), L.ptr(dx), dx.stride(0), dx.stride(1), L.stream_ptr())
+            if dx.dtype != x.dtype:
+                dx = dx.to(x.dtype)
+        if ctx.w_rows is not None and ctx.needs_input_grad[1]:
+            dw = _first_order_grad(g, w_ids, ctx.w_rows)
+        return dx, dw, None
+
+
+class _FmGatherFn(torch.autograd.Function):
+    """FM_Layer: out = rf_fm_fwd(V[ids], w0, w[ids]); dV = rf_fm_bwd's position rows summed per id, dw, dw0."""
+
+    @staticmethod
+    def forward(ctx, V, w, w0, ids):
+        ctx.save_for_backward(V, ids)
+        return fm_forward(V=V, ids=ids, w0=w0, w=w, w_ids=ids)
+
+    @staticmethod
+    def backward(ctx, dout):
+        V, ids = ctx.saved_tensors
+        g = _row_grad(dout)
+        B, fields = ids.shape
+        rows, k = V.shape
+        dV = dw = dw0 = None
+        if ctx.needs_input_grad[0]:
+            kp = (k + 3) // 4 * 4
+            pos = (torch.empty if kp == k else torch.zeros)((B * fields, kp), dtype=torch.float32, device=V.device)
+            L.call("rf_fm_bwd", None, L.DT_F32, 0, 0, L.ptr(V), L.ptr(ids), ids.stride(0), rows, B, fields, k, L.ptr(g),
+                   L.ptr(pos), fields * kp, kp, L.stream_ptr())
+            dV = _dense_row_grad(ids, pos, rows, k)
+        if ctx.needs_input_grad[1]:
+            dw = _first_order_grad(g, ids, rows)
+        if ctx.needs_input_grad[2]:
+            dw0 = g.sum().reshape(1)
+        return dV, dw, dw0, None
+
+
+class _CrossFn(torch.autograd.Function):
+    """out[:, :dim] = rf_cross_fwd(x) written through ldo into a [B, dim + right width] buffer whose right columns
+    take `right` (the concat of DCN); backward = rf_cross_bwd reading its dout in place (lddo)."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, right):
+        B, dim = x.shape
+        extra = 0 if right is None else right.shape[1]
+        out = torch.empty((B, dim + extra), dtype=torch.float32, device=x.device)
+        L.call("rf_cross_fwd", L.ptr(x), L.torch_dtype_code(x.dtype), x.stride(0), B, dim, w.shape[0], L.ptr(w), L.ptr(b),
+               L.ptr(out), out.stride(0), L.stream_ptr())
+        if right is not None:
+            out[:, dim:] = right
+        ctx.save_for_backward(x, w, b)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        x, w, b = ctx.saved_tensors
+        B, dim = x.shape
+        layers = w.shape[0]
+        dout = dout.float()
+        if dout.stride(1) != 1:
+            dout = dout.contiguous()
+        dx = torch.empty((B, dim), dtype=torch.float32, device=x.device)
+        dw, db = torch.empty_like(w), torch.empty_like(b)
+        if B == 0:
+            dw.zero_()
+            db.zero_()
+        wsb = int(L.load().rf_cross_bwd_ws_bytes(B, dim, layers))
+        if wsb == 0:
+            L.check(L.RF_EINVAL, "rf_cross_bwd_ws_bytes")
+        ws = torch.empty(wsb, dtype=torch.uint8, device=x.device)
+        L.call("rf_cross_bwd", L.ptr(x), L.torch_dtype_code(x.dtype), x.stride(0), B, dim, layers, L.ptr(w), L.ptr(b),
+               L.ptr(dout), dout.stride(0), L.ptr(dx), dx.stride(0), L.ptr(dw), L.ptr(db), L.ptr(ws), ws.numel(),
+               L.stream_ptr())
+        if dx.dtype != x.dtype:
+            dx = dx.to(x.dtype)
+        dright = dout[:, dim:] if ctx.needs_input_grad[3] else None
+        return dx, dw, db, dright
+
+
+def _l2(c, t):
+    return c * torch.sum(torch.square(t))
+
+
+class TrainFMLayer(FM_Layer):
+    """FM_Layer under training: gradients reach V, w and w0. The per-id sums of the batch are scattered into dense
+    .grad tensors whose untouched rows are zero, which is what Keras' non-lazy Adam sees for an IndexedSlices gradient.
+    That suits a vocabulary-sized feature_length (a dense optimizer walks every row each step), not the hashed table
+    of the fused encoder, which trains through SparseAdam."""
+
+    def build(self, input_shape=None):
+        super().build(input_shape)
+        for p in (self.w0, self.w, self.V):
+            p.requires_grad_(True)
+
+    def forward(self, inputs: Dict[str, torch.Tensor]) -> torch.Tensor:
+        if self.V is None:
+            self.build()
+        ids = _concat_ids(index_mapping(inputs, self.map_dict), self.V.device)
+        return _FmGatherFn.apply(self.V, self.w, self.w0, ids)
+
+    def regularization(self) -> torch.Tensor:
+        return _l2(self.w_reg, self.w) + _l2(self.v_reg, self.V)
+
+
+class TrainNewFM(New_FM):
+    """New_FM under training: the gradient reaches embed_inputs (rf_fm_bwd, f32 written once) and w (the per-id sums of
+    dout). inputs['sparse_inputs'] may be None or absent: no first-order term (and feature_length may be 0)."""
+
+    def build(self, input_shape=None):
+        super().build(input_shape)
+        self.w.requires_grad_(True)
+
+    def forward(self, inputs, **kwargs) -> torch.Tensor:
+        x = _dense_view(inputs['embed_inputs'])
+        sparse_inputs = inputs.get('sparse_inputs')
+        if sparse_inputs is None:
+            return _FmDenseFn.apply(x, None, None)
+        if self.w is None:
+            self.build()
+        return _FmDenseFn.apply(x, self.w, _concat_ids(sparse_inputs, self.w.device))
+
+    def regularization(self) -> torch.Tensor:
+        return _l2(self.w_reg, self.w)
+
+
+class TrainCrossNetwork(CrossNetwork):
+    """CrossNetwork under training: gradients reach the input, w and b (rf_cross_bwd). forward(x, concat=t) returns
+    [B, dim + t.shape[1]]: the cross output written straight into the left columns of the concat buffer, t in the right
+    ones."""
+
+    def build(self, input_shape):
+        super().build(input_shape)
+        self.w.requires_grad_(True)
+        self.b.requires_grad_(True)
+
+    def forward(self, inputs: torch.Tensor, concat: Optional[torch.Tensor] = None) -> torch.Tensor:
+        if self.w is None:
+            self.build(inputs.shape)
+        if self.layer_num == 0:
+            return inputs if concat is None else torch.cat([inputs.float(), concat], dim=1)
+        x = inputs if inputs.dtype in (torch.float32, torch.bfloat16) else inputs.float()
+        if x.dim() != 2:
+            raise ValueError(f"expected [batch, dim], got {tuple(x.shape)}")
+        if x.shape[1] > 1 and x.stride(1) != 1:
+            x = x.contiguous()
+        return _CrossFn.apply(x, self.w, self.b, concat)
+
+    def regularization(self) -> torch.Tensor:
+        return _l2(self.reg_w, self.w) + _l2(self.reg_b, self.b)

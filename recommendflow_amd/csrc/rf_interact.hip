@@ -3,7 +3,8 @@
 //   rf_cross_fwd  CrossNetwork.call :163-171 (DCN): x_{l+1} = x_0 (x_l . w_l) + b_l + x_l, every layer in one launch
 //   rf_cin_fwd    CIN.call :238-255 (xDeepFM): per layer a GEMM whose A operand (the outer products X0[i,d] X^k[j,d]) is
 //                 generated in registers and never written to HBM
-// All three are deterministic: no floating-point atomics, every reduction in a fixed order.
+// and the backward of the two memory-bound ones, rf_fm_bwd and rf_cross_bwd (described at their kernels below).
+// All are deterministic: no floating-point atomics, every reduction in a fixed order.
 //
 // FM: one wave per example. A lane owns the columns d = lane, lane + 64, ...; the field sum is sequential in f (eight
 // row loads in flight, compensated: the two sums cancel), the column sum and the first-order sum are xor-shuffle
@@ -185,6 +186,443 @@ void dispatch_cross(const void* x, int64_t ldx, int B, int dim, int L, const flo
     else if (dim <= 16384) RF_CROSS(1024, 16);
     else RF_CROSS(1024, 32);
 #undef RF_CROSS
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// FM backward
+// ---------------------------------------------------------------------------------------------------------------
+// de[b][f][d] = g (S[d] - e[b][f][d]), S = sum_f e, g = dout[b]. One wave per example as the forward; a lane's NC =
+// ceil(dim / 64) columns of S stay in registers. Pass 1 forms S (sequential in f, compensated as the forward's field
+// sums: S - e cancels where one field dominates), pass 2 re-reads the rows (L2) and stores dx once. U rows are in
+// flight in both passes (U * NC loads, eight up to dim 512).
+template <typename T, bool GATHER, int NC>
+__global__ __launch_bounds__(256) void fm_bwd_kernel(const T* __restrict__ x, int64_t sb, int64_t sf,
+                                                     const int64_t* __restrict__ ids, int64_t ld_ids, int64_t v_rows, int B,
+                                                     int fields, int dim, const float* __restrict__ dout,
+                                                     float* __restrict__ dx, int64_t dsb, int64_t dsf) {
+    constexpr int U = NC >= 8 ? 1 : 8 / NC;
+    const int lane = threadIdx.x & 63;
+    const int64_t b = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (b >= B) return;
+    const int64_t* idr = GATHER ? ids + b * ld_ids : nullptr;
+    const T* xb = GATHER ? x : x + b * sb;
+    const float nan = __uint_as_float(0x7fc00000u);
+    auto row = [&](int f) -> const T* {
+        if (!GATHER) return xb + (int64_t)f * sf;
+        const int64_t r = idr[f];
+        return r < 0 || r >= v_rows ? nullptr : xb + r * (int64_t)dim;
+    };
+    auto load = [&](const T* r, int j) -> float {
+        const int d = lane + 64 * j;
+        return d < dim ? (r ? ld_f32(r + d) : nan) : 0.f;
+    };
+    float S[NC], C[NC];
+#pragma unroll
+    for (int j = 0; j < NC; ++j) S[j] = C[j] = 0.f;
+    int f = 0;
+    for (; f + U <= fields; f += U) {
+        float e[U][NC];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const T* r = row(f + u);
+#pragma unroll
+            for (int j = 0; j < NC; ++j) e[u][j] = load(r, j);
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+#pragma unroll
+            for (int j = 0; j < NC; ++j) kahan_add(S[j], C[j], e[u][j]);
+        }
+    }
+    for (; f < fields; ++f) {
+        const T* r = row(f);
+#pragma unroll
+        for (int j = 0; j < NC; ++j) kahan_add(S[j], C[j], load(r, j));
+    }
+    const float g = dout[b];
+    float* dxb = dx + b * dsb;
+    f = 0;
+    for (; f + U <= fields; f += U) {
+        float e[U][NC];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const T* r = row(f + u);
+#pragma unroll
+            for (int j = 0; j < NC; ++j) e[u][j] = load(r, j);
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            float* o = dxb + (int64_t)(f + u) * dsf;
+#pragma unroll
+            for (int j = 0; j < NC; ++j) {
+                const int d = lane + 64 * j;
+                if (d < dim) o[d] = g * (S[j] - e[u][j]);
+            }
+        }
+    }
+    for (; f < fields; ++f) {
+        const T* r = row(f);
+        float* o = dxb + (int64_t)f * dsf;
+#pragma unroll
+        for (int j = 0; j < NC; ++j) {
+            const int d = lane + 64 * j;
+            if (d < dim) o[d] = g * (S[j] - load(r, j));
+        }
+    }
+}
+
+// The same backward with the example in registers, for examples large enough to fill a block of 1024 threads: x is
+// read once. With DP = dim padded to a power of two (>= 64) and G = 1024 / DP, thread (fg, d) = (tid / DP, tid % DP)
+// owns the fields fg, fg + G, ... of column d (at most EPT of them). Its compensated partial sum goes to LDS, the G
+// partials of a column are added in order (compensated), and dx is stored from the registers.
+template <typename T, bool GATHER, int EPT>
+__global__ __launch_bounds__(1024) void fm_bwd_reg_kernel(const T* __restrict__ x, int64_t sb, int64_t sf,
+                                                          const int64_t* __restrict__ ids, int64_t ld_ids, int64_t v_rows,
+                                                          int fields, int dim, int dshift, const float* __restrict__ dout,
+                                                          float* __restrict__ dx, int64_t dsb, int64_t dsf) {
+    __shared__ float part[1024];  // [fg][d]: the thread's own slot
+    __shared__ float Ssh[1024];   // S[d]
+    const int tid = threadIdx.x, DP = 1 << dshift, G = 1024 >> dshift;
+    const int d = tid & (DP - 1), fg = tid >> dshift;
+    const int64_t b = blockIdx.x;
+    const int64_t* idr = GATHER ? ids + b * ld_ids : nullptr;
+    const T* xb = GATHER ? x : x + b * sb;
+    const float nan = __uint_as_float(0x7fc00000u);
+    float e[EPT];
+#pragma unroll
+    for (int k = 0; k < EPT; ++k) {
+        const int f = fg + G * k;
+        e[k] = 0.f;
+        if (d < dim && f < fields) {
+            if (GATHER) {
+                const int64_t r = idr[f];
+                e[k] = r < 0 || r >= v_rows ? nan : ld_f32(xb + r * (int64_t)dim + d);
+            } else {
+                e[k] = ld_f32(xb + (int64_t)f * sf + d);
+            }
+        }
+    }
+    float s = 0.f, c = 0.f;
+#pragma unroll
+    for (int k = 0; k < EPT; ++k) kahan_add(s, c, e[k]);
+    part[tid] = s;
+    __syncthreads();
+    if (tid < DP) {
+        float S = 0.f, C = 0.f;
+        for (int g = 0; g < G; ++g) kahan_add(S, C, part[g * DP + tid]);
+        Ssh[tid] = S;
+    }
+    __syncthreads();
+    const float S = Ssh[d], g = dout[b];
+    float* o = dx + b * dsb + d;
+#pragma unroll
+    for (int k = 0; k < EPT; ++k) {
+        const int f = fg + G * k;
+        if (d < dim && f < fields) o[(int64_t)f * dsf] = g * (S - e[k]);
+    }
+}
+
+// the register kernel's shape for (fields, dim): 0 when it does not apply (a small example, or more than 32 fields per
+// thread), else the elements per thread (8, 16, 32); dshift = log2 DP
+inline int fm_bwd_reg_ept(int fields, int dim, int& dshift) {
+    dshift = 6;
+    while ((1 << dshift) < dim) ++dshift;
+    const int G = 1024 >> dshift;
+    const int need = (fields + G - 1) / G;
+    if ((int64_t)fields << dshift < 8192 || need > 32) return 0;
+    return need <= 8 ? 8 : need <= 16 ? 16 : 32;
+}
+
+template <typename T, bool GATHER>
+void dispatch_fm_bwd(const void* x, int64_t sb, int64_t sf, const int64_t* ids, int64_t ld_ids, int64_t v_rows, int B,
+                     int fields, int dim, const float* dout, float* dx, int64_t dsb, int64_t dsf, hipStream_t st) {
+    int dshift;
+    const int ept = fm_bwd_reg_ept(fields, dim, dshift);
+    if (ept) {
+#define RF_FMR(E)                                                                                               \
+    hipLaunchKernelGGL((fm_bwd_reg_kernel<T, GATHER, E>), dim3(B), dim3(1024), 0, st, (const T*)x, sb, sf, ids, ld_ids, \
+                       v_rows, fields, dim, dshift, dout, dx, dsb, dsf)
+        if (ept == 8) RF_FMR(8);
+        else if (ept == 16) RF_FMR(16);
+        else RF_FMR(32);
+#undef RF_FMR
+        return;
+    }
+    const dim3 grid((B + 3) / 4), block(256);
+#define RF_FMB(NC)                                                                                                       \
+    hipLaunchKernelGGL((fm_bwd_kernel<T, GATHER, NC>), grid, block, 0, st, (const T*)x, sb, sf, ids, ld_ids, v_rows, B, \
+                       fields, dim, dout, dx, dsb, dsf)
+    if (dim <= 64) RF_FMB(1);
+    else if (dim <= 128) RF_FMB(2);
+    else if (dim <= 256) RF_FMB(4);
+    else if (dim <= 512) RF_FMB(8);
+    else RF_FMB(16);
+#undef RF_FMB
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Cross backward
+// ---------------------------------------------------------------------------------------------------------------
+// x_l = c_l x_0 + beta_l with c_l = 1 + sum_{m<l} s_m and beta_l = sum_{m<l} b_m, so an example's backward follows from
+// L + 1 dot products of its row: p = dout . x_0 and q_m = w_m . x_0 (t_m = beta_m . w_m does not depend on the example):
+//   s_l = c_l q_l + t_l,   ds_l = p + sum_{m>l} ds_m q_m,   a_l = ds_l c_l
+//   dx   = c_L dout + sum_l a_l w_l
+//   dw_l = sum_b a_l x_0 + beta_l sum_b ds_l,   db_l = sum_b dout + sum_{m>l} w_m sum_b ds_m
+// cross_bwd_const_kernel: t. cross_bwd_row_kernel (the forward's block shapes; x_0 and dout in registers): the dots,
+// dx written once, a and ds of the example to the workspace. cross_bwd_col_kernel: over chunks of kCrossChunk
+// examples, a thread owns a column and adds a_l x_0 and dout in example order. cross_bwd_reduce_kernel adds the chunks
+// in order and applies beta and w. No [B][L][dim] intermediate, no atomics: the same bits on every launch.
+constexpr int kCrossChunk = 128;
+
+struct CrossWs {
+    size_t t, scal, sds, part, total;  // byte offsets
+    int nchunks;
+};
+
+inline size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
+
+inline CrossWs cross_ws(int64_t batch, int dim, int L) {
+    CrossWs l;
+    l.nchunks = (int)((batch + kCrossChunk - 1) / kCrossChunk);
+    l.t = 0;
+    l.scal = align16(kCrossMaxLayers * sizeof(float));
+    l.sds = l.scal + align16((size_t)batch * 2 * L * sizeof(float));
+    l.part = l.sds + align16((size_t)l.nchunks * L * sizeof(float));
+    l.total = l.part + align16((size_t)l.nchunks * (L + 1) * dim * sizeof(float));
+    return l;
+}
+
+// t[l] = sum_d (sum_{m<l} b_m[d]) w_l[d]; one block per layer
+__global__ __launch_bounds__(256) void cross_bwd_const_kernel(const float* __restrict__ w, const float* __restrict__ bias,
+                                                              int dim, float* __restrict__ t) {
+    __shared__ float red[4];
+    const int l = blockIdx.x, tid = threadIdx.x;
+    float s = 0.f;
+    for (int d0 = tid; d0 < dim; d0 += 8 * 256) {  // eight columns per pass: their loads are in flight together
+        float wv[8], beta[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const int d = d0 + 256 * u;
+            wv[u] = d < dim ? w[(int64_t)l * dim + d] : 0.f;
+            beta[u] = 0.f;
+        }
+        for (int m = 0; m < l; ++m) {
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                const int d = d0 + 256 * u;
+                beta[u] += d < dim ? bias[(int64_t)m * dim + d] : 0.f;
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < 8; ++u) s += beta[u] * wv[u];
+    }
+    s = wave_sum(s);
+    if ((tid & 63) == 0) red[tid >> 6] = s;
+    __syncthreads();
+    if (tid == 0) t[l] = ((red[0] + red[1]) + red[2]) + red[3];
+}
+
+template <typename T, int THREADS, int EPT>
+__global__ __launch_bounds__(THREADS) void cross_bwd_row_kernel(const T* __restrict__ x, int64_t ldx, int dim, int L,
+                                                                const float* __restrict__ w,
+                                                                const float* __restrict__ dout, int64_t lddo,
+                                                                float* __restrict__ dx, int64_t lddx,
+                                                                const float* __restrict__ t, float* __restrict__ scal) {
+    constexpr int NW = THREADS / 64;
+    __shared__ float red[kCrossMaxLayers + 1][NW];
+    __shared__ float dots[kCrossMaxLayers + 1];  // p, q_0 .. q_{L-1}
+    __shared__ float coef[kCrossMaxLayers + 1];  // a_0 .. a_{L-1}, c_L
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const T* xr = x + (int64_t)blockIdx.x * ldx;
+    const float* gr = dout + (int64_t)blockIdx.x * lddo;
+    const int ne = tid < dim ? (dim - tid + THREADS - 1) / THREADS : 0;
+    float x0[EPT], g[EPT];
+#pragma unroll
+    for (int e = 0; e < EPT; ++e) {
+        x0[e] = e < ne ? ld_f32(xr + tid + e * THREADS) : 0.f;
+        g[e] = e < ne ? gr[tid + e * THREADS] : 0.f;
+    }
+    {
+        float dot = 0.f;
+#pragma unroll
+        for (int e = 0; e < EPT; ++e) dot += g[e] * x0[e];
+        dot = wave_sum(dot);
+        if (lane == 0) red[0][wave] = dot;
+    }
+    for (int m = 0; m < L; ++m) {
+        const float* wm = w + (int64_t)m * dim;
+        float dot = 0.f;
+#pragma unroll
+        for (int e = 0; e < EPT; ++e) {
+            dot += x0[e] * (e < ne ? wm[tid + e * THREADS] : 0.f);
+            if (e % 8 == 7) __builtin_amdgcn_sched_barrier(0);  // at most eight w loads in flight, as the forward
+        }
+        dot = wave_sum(dot);
+        if (lane == 0) red[m + 1][wave] = dot;
+    }
+    __syncthreads();
+    if (tid <= L) {
+        float s = red[tid][0];
+#pragma unroll
+        for (int v = 1; v < NW; ++v) s += red[tid][v];
+        dots[tid] = s;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        float c = 1.f;
+        for (int l = 0; l < L; ++l) {
+            coef[l] = c;  // c_l until the loop below replaces it with a_l
+            c = c + (c * dots[l + 1] + t[l]);
+        }
+        coef[L] = c;
+        float* sc = scal + (int64_t)blockIdx.x * 2 * L;
+        float r = dots[0];
+        for (int l = L - 1; l >= 0; --l) {
+            const float ds = r;
+            r = r + ds * dots[l + 1];
+            const float a = ds * coef[l];
+            coef[l] = a;
+            sc[l] = a;
+            sc[L + l] = ds;
+        }
+    }
+    __syncthreads();
+    const float cL = coef[L];
+#pragma unroll
+    for (int e = 0; e < EPT; ++e) g[e] = g[e] * cL;
+    for (int m = 0; m < L; ++m) {
+        const float* wm = w + (int64_t)m * dim;
+        const float a = coef[m];
+#pragma unroll
+        for (int e = 0; e < EPT; ++e) {
+            g[e] = g[e] + a * (e < ne ? wm[tid + e * THREADS] : 0.f);
+            if (e % 8 == 7) __builtin_amdgcn_sched_barrier(0);
+        }
+    }
+    float* o = dx + (int64_t)blockIdx.x * lddx;
+#pragma unroll
+    for (int e = 0; e < EPT; ++e) {
+        if (e < ne) o[tid + e * THREADS] = g[e];
+    }
+}
+
+// part[chunk][l][d] = sum_{b in chunk} a[b][l] x_0[b][d] (l < L), part[chunk][L][d] = sum_{b in chunk} dout[b][d],
+// sds[chunk][l] = sum_{b in chunk} ds[b][l]; all in example order. LP: L padded (the accumulators are registers).
+template <typename T, int LP>
+__global__ __launch_bounds__(256) void cross_bwd_col_kernel(const T* __restrict__ x, int64_t ldx,
+                                                            const float* __restrict__ dout, int64_t lddo, int64_t B, int dim,
+                                                            int L, const float* __restrict__ scal, float* __restrict__ sds,
+                                                            float* __restrict__ part) {
+    constexpr int R = 8;  // rows in flight (2 R loads)
+    __shared__ float a[kCrossChunk + R][LP];
+    const int tid = threadIdx.x;
+    const int64_t b0 = (int64_t)blockIdx.x * kCrossChunk;  // chunks on x: their count has no 65535 limit
+    const int nb = (int)min((int64_t)kCrossChunk, B - b0);
+    for (int i = tid; i < (kCrossChunk + R) * LP; i += 256) {
+        const int r = i / LP, l = i % LP;
+        a[r][l] = r < nb && l < L ? scal[(b0 + r) * 2 * L + l] : 0.f;
+    }
+    __syncthreads();
+    if (blockIdx.y == 0 && tid < L) {
+        float s = 0.f;
+        for (int r = 0; r < nb; ++r) s += scal[(b0 + r) * 2 * L + L + tid];
+        sds[(int64_t)blockIdx.x * L + tid] = s;
+    }
+    const int d = blockIdx.y * 256 + tid;
+    if (d >= dim) return;
+    float acc[LP], q = 0.f;
+#pragma unroll
+    for (int l = 0; l < LP; ++l) acc[l] = 0.f;
+    for (int r = 0; r < nb; r += R) {
+        float xv[R], gv[R];
+#pragma unroll
+        for (int u = 0; u < R; ++u) {
+            const bool live = r + u < nb;  // past the chunk: a is zero there and adds nothing
+            xv[u] = live ? ld_f32(x + (b0 + r + u) * ldx + d) : 0.f;
+            gv[u] = live ? dout[(b0 + r + u) * lddo + d] : 0.f;
+        }
+#pragma unroll
+        for (int u = 0; u < R; ++u) {
+            q += gv[u];
+#pragma unroll
+            for (int l = 0; l < LP; ++l) acc[l] += a[r + u][l] * xv[u];
+        }
+    }
+    float* p = part + (int64_t)blockIdx.x * (L + 1) * dim + d;
+#pragma unroll
+    for (int l = 0; l < LP; ++l) {
+        if (l < L) p[(int64_t)l * dim] = acc[l];
+    }
+    p[(int64_t)L * dim] = q;
+}
+
+// the chunks added in order, then dw_l = . + beta_l sum_b ds_l and db_l = sum_b dout + sum_{m>l} w_m sum_b ds_m
+// (64 threads per block: at dim 29184 that is 456 blocks, where 256 threads would leave half of the CUs idle)
+__global__ __launch_bounds__(64) void cross_bwd_reduce_kernel(const float* __restrict__ part, const float* __restrict__ sds,
+                                                               int nchunks, int dim, int L, const float* __restrict__ w,
+                                                               const float* __restrict__ bias, float* __restrict__ dw,
+                                                               float* __restrict__ db) {
+    __shared__ float S[kCrossMaxLayers];
+    const int tid = threadIdx.x;
+    if (tid < L) {
+        float s = 0.f;
+        for (int c = 0; c < nchunks; ++c) s += sds[(int64_t)c * L + tid];
+        S[tid] = s;
+    }
+    __syncthreads();
+    const int d = blockIdx.x * 64 + tid;
+    if (d >= dim) return;
+    const int64_t cs = (int64_t)(L + 1) * dim;  // one chunk of part
+    float beta = 0.f;
+    for (int l = 0; l < L; ++l) {
+        const float* p = part + (int64_t)l * dim + d;
+        float s = 0.f;
+#pragma unroll 8
+        for (int c = 0; c < nchunks; ++c) s += p[c * cs];
+        dw[(int64_t)l * dim + d] = s + beta * S[l];
+        beta += bias[(int64_t)l * dim + d];
+    }
+    const float* p = part + (int64_t)L * dim + d;
+    float acc = 0.f;
+#pragma unroll 8
+    for (int c = 0; c < nchunks; ++c) acc += p[c * cs];
+    for (int l = L - 1; l >= 0; --l) {
+        db[(int64_t)l * dim + d] = acc;
+        acc = acc + w[(int64_t)l * dim + d] * S[l];
+    }
+}
+
+template <typename T>
+void dispatch_cross_bwd(const void* x, int64_t ldx, int B, int dim, int L, const float* w, const float* bias,
+                        const float* dout, int64_t lddo, float* dx, int64_t lddx, float* dw, float* db, char* ws,
+                        const CrossWs& lay, hipStream_t st) {
+    float* t = reinterpret_cast<float*>(ws + lay.t);
+    float* scal = reinterpret_cast<float*>(ws + lay.scal);
+    float* sds = reinterpret_cast<float*>(ws + lay.sds);
+    float* part = reinterpret_cast<float*>(ws + lay.part);
+    hipLaunchKernelGGL(cross_bwd_const_kernel, dim3(L), dim3(256), 0, st, w, bias, dim, t);
+#define RF_CROSSB(TH, E)                                                                                                  \
+    hipLaunchKernelGGL((cross_bwd_row_kernel<T, TH, E>), dim3(B), dim3(TH), 0, st, (const T*)x, ldx, dim, L, w, dout, lddo, \
+                       dx, lddx, t, scal)
+    if (dim <= 256) RF_CROSSB(256, 1);
+    else if (dim <= 512) RF_CROSSB(256, 2);
+    else if (dim <= 1024) RF_CROSSB(256, 4);
+    else if (dim <= 2048) RF_CROSSB(256, 8);
+    else if (dim <= 4096) RF_CROSSB(256, 16);
+    else if (dim <= 8192) RF_CROSSB(1024, 8);
+    else if (dim <= 16384) RF_CROSSB(1024, 16);
+    else RF_CROSSB(1024, 32);
+#undef RF_CROSSB
+    const dim3 grid(lay.nchunks, (dim + 255) / 256);
+#define RF_CROSSC(LP)                                                                                                  \
+    hipLaunchKernelGGL((cross_bwd_col_kernel<T, LP>), grid, dim3(256), 0, st, (const T*)x, ldx, dout, lddo, (int64_t)B, \
+                       dim, L, scal, sds, part)
+    if (L <= 4) RF_CROSSC(4);
+    else if (L <= 8) RF_CROSSC(8);
+    else RF_CROSSC(16);
+#undef RF_CROSSC
+    hipLaunchKernelGGL(cross_bwd_reduce_kernel, dim3((dim + 63) / 64), dim3(64), 0, st, part, sds, lay.nchunks, dim, L, w,
+                       bias, dw, db);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -560,4 +998,56 @@ extern "C" int rf_cin_fwd(const void* x, int32_t x_dtype, int64_t x_stride_b, in
     hipLaunchKernelGGL(cin_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, a.part, total, a.p.sumH,
                        a.p.dsub, out, ldo);
     return rf_check_launch("rf_cin_fwd");
+}
+
+extern "C" int rf_fm_bwd(const void* x, int32_t x_dtype, int64_t x_stride_b, int64_t x_stride_f, const float* V,
+                         const int64_t* ids, int64_t ld_ids, int64_t v_rows, int32_t batch, int32_t fields, int32_t dim,
+                         const float* dout, float* dx, int64_t dx_stride_b, int64_t dx_stride_f, void* stream) {
+    RF_REQUIRE(batch >= 0, "rf_fm_bwd: batch must be >= 0");
+    RF_REQUIRE(dim >= 1 && dim <= kFmMaxDim, "rf_fm_bwd: dim (%d) must be in [1, %d]", dim, kFmMaxDim);
+    RF_REQUIRE(fields >= 1 && fields <= kFmMaxFields, "rf_fm_bwd: fields (%d) must be in [1, %d]", fields, kFmMaxFields);
+    RF_REQUIRE((x != nullptr) != (V != nullptr), "rf_fm_bwd: give exactly one of x (dense) and V (gathered)");
+    if (x) {
+        RF_REQUIRE(x_dtype == RF_DTYPE_F32 || x_dtype == RF_DTYPE_BF16, "rf_fm_bwd: x_dtype must be F32 or BF16");
+        RF_REQUIRE(x_stride_f >= dim && x_stride_b >= 0, "rf_fm_bwd: x_stride_f must be >= dim");
+    } else {
+        RF_REQUIRE(ids && ld_ids >= fields && v_rows >= 1, "rf_fm_bwd: the gathered form needs ids, ld_ids >= fields, v_rows >= 1");
+    }
+    RF_REQUIRE(dx_stride_f >= dim && dx_stride_b >= (int64_t)(fields - 1) * dx_stride_f + dim,
+               "rf_fm_bwd: dx_stride_f must be >= dim and dx_stride_b >= (fields - 1) * dx_stride_f + dim");
+    if (batch == 0) return RF_OK;
+    RF_REQUIRE(dout && dx, "rf_fm_bwd: dout or dx is null");
+    hipStream_t st = rf_stream(stream);
+    if (V) dispatch_fm_bwd<float, true>(V, 0, 0, ids, ld_ids, v_rows, batch, fields, dim, dout, dx, dx_stride_b, dx_stride_f, st);
+    else if (x_dtype == RF_DTYPE_F32)
+        dispatch_fm_bwd<float, false>(x, x_stride_b, x_stride_f, nullptr, 0, 0, batch, fields, dim, dout, dx, dx_stride_b, dx_stride_f, st);
+    else
+        dispatch_fm_bwd<uint16_t, false>(x, x_stride_b, x_stride_f, nullptr, 0, 0, batch, fields, dim, dout, dx, dx_stride_b, dx_stride_f, st);
+    return rf_check_launch("rf_fm_bwd");
+}
+
+extern "C" size_t rf_cross_bwd_ws_bytes(int32_t batch, int32_t dim, int32_t n_layers) {
+    if (batch < 0 || dim < 1 || dim > kCrossMaxDim || n_layers < 1 || n_layers > kCrossMaxLayers) return 0;
+    return cross_ws(batch, dim, n_layers).total;
+}
+
+extern "C" int rf_cross_bwd(const void* x, int32_t x_dtype, int64_t ldx, int32_t batch, int32_t dim, int32_t n_layers,
+                            const float* w, const float* b, const float* dout, int64_t lddo, float* dx, int64_t lddx,
+                            float* dw, float* db, void* ws, size_t ws_bytes, void* stream) {
+    RF_REQUIRE(batch >= 0, "rf_cross_bwd: batch must be >= 0");
+    RF_REQUIRE(n_layers >= 1 && n_layers <= kCrossMaxLayers, "rf_cross_bwd: n_layers (%d) must be in [1, %d]", n_layers, kCrossMaxLayers);
+    RF_REQUIRE(dim >= 1 && dim <= kCrossMaxDim, "rf_cross_bwd: dim (%d) must be in [1, %d]", dim, kCrossMaxDim);
+    RF_REQUIRE(x_dtype == RF_DTYPE_F32 || x_dtype == RF_DTYPE_BF16, "rf_cross_bwd: x_dtype must be F32 or BF16");
+    RF_REQUIRE(ldx >= dim && lddo >= dim && lddx >= dim, "rf_cross_bwd: ldx, lddo and lddx must be >= dim");
+    if (batch == 0) return RF_OK;
+    RF_REQUIRE(x && w && b && dout && dx && dw && db, "rf_cross_bwd: null pointer");
+    RF_REQUIRE(ws && ((uintptr_t)ws & 15) == 0, "rf_cross_bwd: null or misaligned workspace");
+    const CrossWs lay = cross_ws(batch, dim, n_layers);
+    RF_REQUIRE(ws_bytes >= lay.total, "rf_cross_bwd: ws_bytes too small (%zu < %zu)", ws_bytes, lay.total);
+    hipStream_t st = rf_stream(stream);
+    if (x_dtype == RF_DTYPE_F32)
+        dispatch_cross_bwd<float>(x, ldx, batch, dim, n_layers, w, b, dout, lddo, dx, lddx, dw, db, static_cast<char*>(ws), lay, st);
+    else
+        dispatch_cross_bwd<uint16_t>(x, ldx, batch, dim, n_layers, w, b, dout, lddo, dx, lddx, dw, db, static_cast<char*>(ws), lay, st);
+    return rf_check_launch("rf_cross_bwd");
 }

@@ -1,0 +1,171 @@
+"""GPU: TrainableDeepFM and TrainableDCN (6 slots, D 8, a 3600-row table, hidden units 32 -> 16) against the float64
+restatement (tests/interact_train_ref.py) composed from the model's own parameters and the GPU's own embed output.
+Tolerance per tensor as in test_interact_train_gpu: err <= 8 x the float32-CPU restatement's err, floor 2^-20."""
+import numpy as np
+import pytest
+import torch
+
+import interact_train_ref as T
+from recommendflow_amd.backend.encoder.sparse_encoder import FusedSparseEncoder, SlotSpec
+from recommendflow_amd.models.ranking.dcn import TrainableDCN
+from recommendflow_amd.models.ranking.deepfm import TrainableDeepFM
+from recommendflow_amd.runtime.batch import synthetic_batch
+
+pytestmark = pytest.mark.gpu
+
+S, D, HIDDEN, FIRST_ROWS, FIRST_N = 6, 8, (32, 16), 50, 3
+KINDS = ["deepfm", "deepfm_first", "dcn"]
+
+
+def _model(kind, dropout=0.0, seed=1, enc_seed=4, lr=0.01):
+    specs = [SlotSpec(f"f{s}", 600, (2022, 2023), ["sum", "avg"][s % 2]) for s in range(S)]
+    enc = FusedSparseEncoder(specs, D, seed=enc_seed)
+    if kind == "dcn":
+        return TrainableDCN(enc, layer_num=3, hidden_units=HIDDEN, dropout=dropout, reg_w=0.01, reg_b=0.02,
+                            learning_rate=lr, seed=seed)
+    rows = FIRST_ROWS if kind == "deepfm_first" else 0
+    return TrainableDeepFM(enc, hidden_units=HIDDEN, dropout=dropout, first_order_rows=rows, w_reg=0.01,
+                           learning_rate=lr, seed=seed)
+
+
+def _batch(B, seed=3):
+    return synthetic_batch(B, [s % 2 == 1 for s in range(S)], seed=seed, id_max=400, uniform=True).to("cuda")
+
+
+def _labels(B):
+    return (torch.arange(B, device="cuda") % 2).float()
+
+
+def _inputs(kind, B):
+    """The model's keyword inputs: first_ids int64 [B, n] for the DeepFM with a first-order term."""
+    if kind != "deepfm_first":
+        return {}
+    g = torch.Generator().manual_seed(B)
+    return {"first_ids": torch.randint(0, FIRST_ROWS, (B, FIRST_N), generator=g).to("cuda")}
+
+
+def _check(name, got, want64, want32):
+    err, bar = T.rel_err(got, want64), T.bar(want32, want64)
+    print(f"{name}: err {err:.3e} bar {bar:.3e} (float32 CPU err {T.rel_err(want32, want64):.3e})")
+    assert bool(torch.isfinite(got).all()) and err <= bar, (name, err, bar)
+
+
+def _restated_logits(kind, model, P, x, inputs, training):
+    if kind == "dcn":
+        return T.dcn(model, P, x, training)
+    return T.deepfm(model, P, x, inputs.get("first_ids"), training)
+
+
+def _restated_step(kind, model, x, y, inputs, dtype):
+    P = T.model_params(model, dtype)
+    xr = x.to(dtype).requires_grad_(True)
+    yr = y.cpu().to(dtype)
+    if kind == "dcn":
+        lv = T.dcn_loss(model, P, xr, yr)
+    else:
+        lv = T.deepfm_loss(model, P, xr, yr, inputs.get("first_ids"))
+    lv.backward()
+    return lv.detach(), {n: p.grad for n, p in P.items()}, xr.grad
+
+
+@pytest.mark.parametrize("B", [64, 63])
+@pytest.mark.parametrize("kind", KINDS)
+def test_training_step_against_float64(cuda, kind, B):
+    """dropout = 0: the loss, every dense parameter's gradient and the gradient reaching the embed output. B = 63 is no
+    multiple of 4: the weight-gradient GEMMs (contraction over the batch) take the counted torch fallback."""
+    model = _model(kind)
+    hb, y, inputs = _batch(B), _labels(B), _inputs(kind, B)
+    x = model.enc(hb).detach().cpu()
+    seen = {}
+    model.train()
+    logits = model(hb, embed_hook=lambda gr: seen.setdefault("g", gr.detach().clone()), **inputs)
+    assert logits.shape == (B,)
+    lv = model.loss(y, logits)
+    lv.backward()
+    torch.cuda.synchronize()
+    assert model.enc.grad is not None and model.enc.grad.count() > 0
+    l64, g64, dx64 = _restated_step(kind, model, x, y, inputs, torch.float64)
+    l32, g32, dx32 = _restated_step(kind, model, x, y, inputs, torch.float32)
+    _check(f"{kind} loss B{B}", lv.detach().reshape(1), l64.reshape(1), l32.reshape(1))
+    named = dict(model.named_parameters())
+    assert set(named) == set(g64)
+    want_names = {"dcn": {"cross.w", "cross.b"}, "deepfm_first": {"fm.w"}, "deepfm": set()}[kind]
+    assert want_names <= set(named) and ("fm.w" in named) == (kind == "deepfm_first")
+    for n, p in named.items():
+        assert p.grad is not None, n
+        _check(f"{kind} grad {n} B{B}", p.grad, g64[n], g32[n])
+    _check(f"{kind} grad embed output B{B}", seen["g"], dx64, dx32)
+
+
+@pytest.mark.parametrize("kind", KINDS)
+def test_eval_forward(cuda, kind):
+    model = _model(kind, dropout=0.3)
+    hb, inputs = _batch(64), _inputs(kind, 64)
+    model.step(hb, _labels(64), **inputs)  # moving statistics and parameters away from their initial values
+    model.eval()
+    out = model(hb, **inputs)
+    assert out.shape == (64,) and not out.requires_grad
+    assert torch.equal(out, model(hb, **inputs)), "the eval forward is not deterministic (dropout left on?)"
+    x = model.enc(hb).detach().cpu()
+    ref = {}
+    for dt in (torch.float64, torch.float32):
+        with torch.no_grad():
+            P = T.model_params(model, dt)
+            ref[dt] = torch.sigmoid(_restated_logits(kind, model, P, x.to(dt), inputs, training=False))
+    _check(f"{kind} eval", out, ref[torch.float64], ref[torch.float32])
+
+
+def _run_steps(kind, n, seed):
+    model = _model(kind, dropout=0.3, seed=seed)
+    hb, y, inputs = _batch(64, seed=8), _labels(64), _inputs(kind, 64)
+    plan = model.enc.backward_plan(hb)
+    rows = plan.rows[: int(plan.n_uniq)].long().clone()
+    t0 = model.embedding_table().clone()
+    losses = [model.step(hb, y, **inputs).cpu().numpy().view(np.uint32).item() for _ in range(n)]
+    return model, losses, rows, t0
+
+
+@pytest.mark.parametrize("kind", KINDS)
+def test_thirty_steps(cuda, kind):
+    model, bits, rows, t0 = _run_steps(kind, 30, 3)
+    losses = np.array(bits, np.uint32).view(np.float32)
+    print(kind, "losses", losses.tolist())
+    assert np.isfinite(losses).all()
+    assert losses[-1] < losses[0]
+    t1 = model.embedding_table()
+    assert rows.numel() > 0 and bool((t1[rows] != t0[rows]).any(dim=1).all()), "a touched table row did not move"
+    assert model.sparse_opt.iterations == 30 and model.dense_opt.iterations == 30
+    _, bits2, _, _ = _run_steps(kind, 30, 3)
+    assert bits == bits2, "equal seeds gave different runs"
+
+
+@pytest.mark.parametrize("kind", KINDS)
+def test_checkpoint_round_trip(cuda, kind):
+    hb, y, inputs = _batch(64, seed=8), _labels(64), _inputs(kind, 64)
+    a = _model(kind, dropout=0.3, seed=3)
+    for _ in range(3):
+        a.step(hb, y, **inputs)
+    sd = {k: v.detach().clone() for k, v in a.state_dict().items()}
+    assert any(k.startswith("dense_m.") for k in sd) and "sparse_m" in sd
+    b = _model(kind, dropout=0.3, seed=3, enc_seed=9)  # another table: everything must come from the checkpoint
+    assert not torch.equal(a.enc.table, b.enc.table)
+    b.load_state_dict(sd)
+    la, lb = a.step(hb, y, **inputs), b.step(hb, y, **inputs)
+    assert la.cpu().numpy().view(np.uint32).item() == lb.cpu().numpy().view(np.uint32).item()
+    assert torch.equal(a.embedding_table(), b.embedding_table())
+    for p, q in zip(a.parameters(), b.parameters()):
+        assert torch.equal(p, q)
+
+
+@pytest.mark.parametrize("kind", KINDS)
+def test_step_refuses_data_parallel(cuda, kind):
+    model = _model(kind)
+    with pytest.raises(NotImplementedError):
+        model.step(_batch(8), _labels(8), dp=object(), **_inputs(kind, 8))
+
+
+def test_deepfm_first_ids_must_match_the_configuration(cuda):
+    with pytest.raises(ValueError):
+        _model("deepfm").step(_batch(8), _labels(8), first_ids=torch.zeros(8, 2, dtype=torch.int64, device="cuda"))
+    with pytest.raises(ValueError):
+        _model("deepfm_first").step(_batch(8), _labels(8))
