@@ -664,9 +664,27 @@ def gelu_grad(x):
     return 0.5 * (1.0 + erf(x / math.sqrt(2.0))) + x * np.exp(-0.5 * x * x) / math.sqrt(2.0 * math.pi)
 
 
-def ln_mlp_train_fwd(x, layers, rate: float, seeds, eps: float = 1e-6):
+def activation_grad(x, act: str):
+    """d act / dx at the pre-activation x for gelu | relu | selu | none, as rf_tower.hip's act_vd and TF take it:
+    relu's is x > 0 (0 at the kink), selu's is scale for x > 0 and scale alpha exp(x) elsewhere."""
+    x = np.asarray(x, np.float64)
+    if act in (None, "none", "linear"):
+        return np.ones_like(x)
+    if act == "gelu":
+        return gelu_grad(x)
+    if act == "relu":
+        return (x > 0).astype(np.float64)
+    if act == "selu":
+        alpha, scale = 1.6732632423543772848170429916717, 1.0507009873554804934193349852946
+        return scale * np.where(x > 0, 1.0, alpha * np.exp(np.minimum(x, 0)))
+    raise ValueError(act)
+
+
+def ln_mlp_train_fwd(x, layers, rate: float, seeds, eps: float = 1e-6, act: str = "gelu"):
     """layers: [{"W": [N][K], "b", "gamma", "beta"}] (W stored [out][in], as librf); per layer LayerNormalization
-    (tf.nn.moments: biased variance) -> Dense -> gelu -> Dropout(rate). Returns (h, cache)."""
+    (tf.nn.moments: biased variance) -> Dense -> act (gelu | relu | selu | none) -> Dropout(rate). Returns (h, cache)."""
+    if act not in ("gelu", "relu", "selu", "none"):
+        raise ValueError(act)
     h = np.asarray(x, np.float64)
     cache = []
     for p, seed in zip(layers, seeds):
@@ -678,19 +696,19 @@ def ln_mlp_train_fwd(x, layers, rate: float, seeds, eps: float = 1e-6):
         z = xhat * p["gamma"] + p["beta"]
         pre = z @ W.T + p["b"]
         keep = dropout_keep(seed, h.shape[0], W.shape[0], rate) if rate > 0 else np.ones(pre.shape, bool)
-        out = np.where(keep, gelu(pre) / (1.0 - rate), 0.0)
+        out = np.where(keep, activation(pre, act) / (1.0 - rate), 0.0)
         cache.append({"h": h, "xhat": xhat, "rstd": rstd, "z": z, "pre": pre, "keep": keep})
         h = out
     return h, cache
 
 
-def ln_mlp_train_bwd(dout, layers, cache, rate: float):
-    """Backward of ln_mlp_train_fwd: (dx, [{"W", "b", "gamma", "beta"} gradients])."""
+def ln_mlp_train_bwd(dout, layers, cache, rate: float, act: str = "gelu"):
+    """Backward of ln_mlp_train_fwd (the same act): (dx, [{"W", "b", "gamma", "beta"} gradients])."""
     dh = np.asarray(dout, np.float64)
     grads = []
     for p, c in zip(reversed(layers), reversed(cache)):
         W = np.asarray(p["W"], np.float64)
-        dpre = np.where(c["keep"], dh / (1.0 - rate), 0.0) * gelu_grad(c["pre"])
+        dpre = np.where(c["keep"], dh / (1.0 - rate), 0.0) * activation_grad(c["pre"], act)
         dz = dpre @ W
         u = dz * p["gamma"]
         xh = c["xhat"]

@@ -11,7 +11,9 @@ and backward
     dW = dpre^T z, dz = dpre W         rf_gemm_f32 (weight-gradient and input-gradient layouts)
     dx, dgamma, dbeta = rf_layernorm_bwd(dz, x)
 Explicit forward / backward (no torch autograd): the caches are the layer inputs, the normalised inputs and the
-pre-activations. Parameters are fp32 tensors with .grad set by backward() (backend.optim.KerasAdam steps them).
+pre-activations. Any batch size and any widths: where one is no multiple of 4 the GEMM operands are zero-padded
+buffers (_gemm_operands), the element-wise and LayerNorm kernels run on the logical [M, width] blocks inside them.
+Parameters are fp32 tensors with .grad set by backward() (backend.optim.KerasAdam steps them).
 Keras initialisers: Dense glorot_uniform kernel, zero bias; LayerNorm gamma 1, beta 0.
 """
 from __future__ import annotations
@@ -60,6 +62,21 @@ class TrainLNMLP:
     def layer_seeds(self, step: int) -> List[int]:
         return [layer_seed(self.seed, step, l) for l in range(len(self.units))]
 
+    @staticmethod
+    def _gemm_operands(M: int, K: int, u: int, W: torch.Tensor):
+        """The layer's GEMM operands: rf_gemm_f32 takes contraction lengths and leading dimensions in multiples of 4,
+        and the three products contract over K (forward), M (weight gradient) and u (input gradient). When all three
+        are multiples of 4 these are an empty [M, K] buffer for the normalised input and W itself; otherwise
+        zero-filled buffers with each dimension rounded up to 4 (W copied into its corner), whose pad rows and columns
+        add exact zeros to every product."""
+        if not (M | K | u) & 3:
+            return torch.empty((M, K), dtype=torch.float32, device=W.device), W
+        Mp, Kp, up = (-(-n // 4) * 4 for n in (M, K, u))
+        zbuf = torch.zeros((Mp, Kp), dtype=torch.float32, device=W.device)
+        Wp = torch.zeros((up, Kp), dtype=torch.float32, device=W.device)
+        Wp[:u, :K] = W
+        return zbuf, Wp
+
     def forward(self, x: torch.Tensor, step: int = 0, out: Optional[torch.Tensor] = None, training: bool = True,
                 stream=None) -> torch.Tensor:
         """x [M, in] fp32 (unit column stride, any row stride) -> [M, units[-1]]; `out` (optional view, any row
@@ -74,13 +91,14 @@ class TrainLNMLP:
         last = len(self.units) - 1
         for l, u in enumerate(self.units):
             K = x.shape[1]
-            z = torch.empty((M, K), dtype=torch.float32, device=x.device)
+            zbuf, Wp = self._gemm_operands(M, K, u, self.W[l])
+            z = zbuf[:M, :K]
             L.call("rf_norm_fwd", L.ptr(x), M, K, x.stride(0), 0, self.eps, L.ptr(self.gamma[l]), L.ptr(self.beta[l]), None,
                    None, L.ptr(z), L.DT_F32, z.stride(0), st)
-            pre = GM.gemm_f32(z, self.W[l], trans_b=True, bias=self.b[l], stream=st)
+            pre = GM.gemm_f32(zbuf[:M], Wp[:u], trans_b=True, bias=self.b[l], stream=st)
             h = out if (l == last and out is not None) else torch.empty((M, u), dtype=torch.float32, device=x.device)
             L.call("rf_act_dropout_fwd", L.ptr(pre), pre.stride(0), M, u, self.act, rate, seeds[l], L.ptr(h), h.stride(0), st)
-            cache.append((x, z, pre))
+            cache.append((x, zbuf, Wp, pre))
             x = h
         self._cache = (cache, rate, seeds)
         return x
@@ -97,17 +115,21 @@ class TrainLNMLP:
             dh = dh.contiguous()
         dx = None
         for l in reversed(range(len(self.units))):
-            x, z, pre = cache[l]
+            x, zbuf, Wp, pre = cache[l]
             M, N = pre.shape
-            K = z.shape[1]
-            dpre = torch.empty((M, N), dtype=torch.float32, device=pre.device)
+            K = x.shape[1]
+            Mp, Np = zbuf.shape[0], Wp.shape[0]
+            padded = (Mp, Np) != (M, N)
+            dpbuf = (torch.zeros if padded else torch.empty)((Mp, Np), dtype=torch.float32, device=pre.device)
+            dpre = dpbuf[:M, :N]
             db = torch.empty(N, dtype=torch.float32, device=pre.device)
             ws = torch.empty(max(int(lib.rf_tower_ws_bytes(M, N)), 4), dtype=torch.uint8, device=pre.device)
             L.call("rf_act_dropout_bwd", L.ptr(dh), dh.stride(0), L.ptr(pre), pre.stride(0), M, N, self.act, rate, seeds[l],
                    L.ptr(dpre), dpre.stride(0), L.ptr(db), L.ptr(ws), ws.numel(), st)
-            self.W[l].grad = GM.gemm_f32(dpre, z, trans_a=True, stream=st)
+            dW = GM.gemm_f32(dpbuf, zbuf, trans_a=True, stream=st)
+            self.W[l].grad = dW if dW.shape == self.W[l].shape else dW[:N, :K].contiguous()
             self.b[l].grad = db
-            dz = GM.gemm_f32(dpre, self.W[l], stream=st)
+            dz = GM.gemm_f32(dpbuf[:M], Wp, stream=st)[:, :K]
             dxl = torch.empty((M, K), dtype=torch.float32, device=pre.device)
             dg = torch.empty(K, dtype=torch.float32, device=pre.device)
             dbt = torch.empty(K, dtype=torch.float32, device=pre.device)

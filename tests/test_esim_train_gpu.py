@@ -92,29 +92,74 @@ def test_esim_train_tie_counts(cuda):
     np.testing.assert_array_equal(aux[:, :d].cpu().numpy(), cnt)
 
 
-def test_ln_mlp_train_vs_oracle(cuda):
+def _ln_mlp(K, units, act, rate=0.3, seed=3):
     from recommendflow_amd.backend.blocks.train_ln_mlp import TrainLNMLP
 
-    M, K = 300, 48
-    mlp = TrainLNMLP(K, (64, 32), rate=0.3, activation="gelu", seed=3)
+    mlp = TrainLNMLP(K, units, rate=rate, activation=act, seed=seed)
     for p in mlp.gamma + mlp.beta:  # non-trivial LayerNorm parameters
         p.add_(torch.randn(p.shape, generator=torch.Generator().manual_seed(p.numel())).cuda() * 0.1)
+    return mlp
+
+
+@pytest.mark.parametrize("M,K,units,act", [(300, 48, (64, 32), "gelu"), (301, 50, (70, 33), "none"), (301, 50, (70, 33), "gelu"),
+                                           (301, 50, (70, 33), "relu"), (301, 50, (70, 33), "selu"), (5, 130, (1, 66), "gelu")],
+                         ids=lambda v: "x".join(map(str, v)) if isinstance(v, tuple) else str(v))
+def test_ln_mlp_train_vs_oracle(cuda, M, K, units, act):
+    """(301, 50, (70, 33)): widths that are no multiple of 4 (the scalar kernels), a row count that is none (the
+    LayerNorm row tail), a lane loop's second trip (70), under each activation; (5, 130, (1, 66)): one-column layers."""
+    mlp = _ln_mlp(K, units, act)
     g = torch.Generator().manual_seed(1)
     x = torch.randn((M, K), generator=g) * 2 + 0.5
     h = mlp.forward(x.cuda(), step=7)
-    layers = [{"W": mlp.W[i].cpu().double().numpy(), "b": mlp.b[i].cpu().double().numpy(),
-               "gamma": mlp.gamma[i].cpu().double().numpy(), "beta": mlp.beta[i].cpu().double().numpy()} for i in range(2)]
-    want, cache = O.ln_mlp_train_fwd(x.double().numpy(), layers, 0.3, mlp.layer_seeds(7))
+    layers = _oracle_layers(mlp)
+    want, cache = O.ln_mlp_train_fwd(x.double().numpy(), layers, 0.3, mlp.layer_seeds(7), act=act)
     close(h.cpu().numpy(), want, 1e-5, "h")
     dh = torch.randn(h.shape, generator=g)
     dx = mlp.backward(dh.cuda())
-    wdx, grads = O.ln_mlp_train_bwd(dh.double().numpy(), layers, cache, 0.3)
+    wdx, grads = O.ln_mlp_train_bwd(dh.double().numpy(), layers, cache, 0.3, act=act)
     close(dx.cpu().numpy(), wdx, 1e-4, "dx")
     for i in range(2):
         close(mlp.W[i].grad.cpu().numpy(), grads[i]["W"], 1e-4, f"W{i}")
         close(mlp.b[i].grad.cpu().numpy(), grads[i]["b"], 1e-4, f"b{i}")
         close(mlp.gamma[i].grad.cpu().numpy(), grads[i]["gamma"], 1e-4, f"gamma{i}")
         close(mlp.beta[i].grad.cpu().numpy(), grads[i]["beta"], 1e-4, f"beta{i}")
+
+
+def test_ln_mlp_out_view_eval_mode_and_need_dx(cuda):
+    """forward(out=view) writes the last layer into a column block of a wider tensor and nothing beside it;
+    training=False is the rate-0 oracle whatever the layer's rate; backward(need_dx=False) returns None and leaves
+    the same parameter gradients as need_dx=True."""
+    M, K, units = 37, 50, (70, 33)
+    mlp = _ln_mlp(K, units, "gelu")
+    g = torch.Generator().manual_seed(2)
+    x = (torch.randn((M, K), generator=g) * 2 + 0.5).cuda()
+    layers = _oracle_layers(mlp)
+    wide = torch.full((M, 5 + units[-1] + 3), float("nan"), device="cuda")
+    view = wide[:, 5: 5 + units[-1]]
+    h = mlp.forward(x, step=7, out=view)
+    assert h.data_ptr() == view.data_ptr()
+    want, cache = O.ln_mlp_train_fwd(x.cpu().double().numpy(), layers, 0.3, mlp.layer_seeds(7))
+    close(view.cpu().numpy(), want, 1e-5, "h")
+    assert torch.isnan(wide[:, :5]).all() and torch.isnan(wide[:, 5 + units[-1]:]).all()
+    dh = torch.randn((M, units[-1]), generator=g).cuda()
+    dx = mlp.backward(dh)
+    wdx, grads = O.ln_mlp_train_bwd(dh.cpu().double().numpy(), layers, cache, 0.3)
+    close(dx.cpu().numpy(), wdx, 1e-4, "dx")
+    kept = [p.grad.clone() for p in mlp.parameters()]
+    for i in range(2):
+        for j, k in enumerate(("W", "b", "gamma", "beta")):  # the order of parameters()
+            close(kept[4 * i + j].cpu().numpy(), grads[i][k], 1e-4, f"{k}{i}")
+    for p in mlp.parameters():
+        p.grad = None
+    mlp.forward(x, step=7, out=view)
+    assert mlp.backward(dh, need_dx=False) is None
+    for p, q in zip(mlp.parameters(), kept):
+        assert torch.equal(p.grad, q)
+    # inference: no dropout
+    he = mlp.forward(x, step=7, training=False)
+    want0, _ = O.ln_mlp_train_fwd(x.cpu().double().numpy(), layers, 0.0, mlp.layer_seeds(7))
+    close(he.cpu().numpy(), want0, 1e-5, "eval h")
+    assert (he != 0).all()  # nothing dropped (gelu is 0 only at 0)
 
 
 def test_softmax_ce_loss(cuda):

@@ -2,7 +2,9 @@
 finite differences of its own forward. This pins the analytic backward the GPU training path is checked against
 (tests/test_esim_train_gpu.py): for every parameter group a random direction v, (f(t + h v) - f(t - h v)) / 2h vs
 <grad, v>, rtol 1e-6 in float64. The forward follows esim.py:45-53,69-89, attention_layers.py:33-74, mlp.py:4-15;
-parity of the forward itself with the reference is unpinned (TensorFlow is not importable)."""
+parity of the forward itself with the reference is unpinned (TensorFlow is not importable).
+ln_mlp_train_fwd / _bwd are pinned the same way on their own for each activation TrainLNMLP accepts (gelu, relu, selu,
+none), with every pre-activation kept away from relu's and selu's kink at 0."""
 import numpy as np
 import pytest
 
@@ -66,3 +68,68 @@ def test_esim_train_grads_match_finite_differences(rate):
     for name, fd, an in checks:
         assert abs(fd - an) <= 1e-6 * max(1.0, abs(fd)) + 1e-9, (name, fd, an)
     assert np.isfinite(loss)
+
+
+def _ln_mlp_case(act, rate, margin=1e-3):
+    """A two-layer LayerNorm MLP whose every pre-activation keeps `margin` from 0: relu and selu are not
+    differentiable there (selu's slope jumps from scale alpha to scale), and the finite-difference step moves a
+    pre-activation by ~1e-5 at most. Redrawn from consecutive seeds until the margin holds (about 9 draws in 10 do)."""
+    for seed in range(100, 140):
+        rng = np.random.default_rng(seed)
+        M, k = 6, 5
+        layers = []
+        for u in (8, 7):
+            layers.append({"W": rng.normal(0, 0.6, (u, k)), "b": rng.normal(0, 0.3, u), "gamma": 1 + rng.normal(0, 0.1, k),
+                           "beta": rng.normal(0, 0.1, k)})
+            k = u
+        x = rng.normal(0, 1.0, (M, 5))
+        R = rng.normal(size=(M, k))
+        _, cache = O.ln_mlp_train_fwd(x, layers, rate, [21, 22], act=act)
+        if min(np.abs(c["pre"]).min() for c in cache) >= margin:
+            return rng, x, layers, R
+    raise AssertionError("no draw kept the margin")
+
+
+@pytest.mark.parametrize("rate", [0.0, 0.3])
+@pytest.mark.parametrize("act", ["relu", "selu", "none", "gelu"])
+def test_ln_mlp_train_grads_match_finite_differences(act, rate):
+    """ln_mlp_train_bwd(act=...) against central differences of ln_mlp_train_fwd(act=...) on f = <h, R>: the input
+    and every parameter group, the step and the bar of the gelu pin above."""
+    rng, x, layers, R = _ln_mlp_case(act, rate)
+    seeds = [21, 22]
+
+    def f(x_=x, layers_=layers):
+        return (O.ln_mlp_train_fwd(x_, layers_, rate, seeds, act=act)[0] * R).sum()
+
+    h, cache = O.ln_mlp_train_fwd(x, layers, rate, seeds, act=act)
+    assert min(np.abs(c["pre"]).min() for c in cache) >= 1e-3
+    if act in ("relu", "selu"):
+        assert all((c["pre"] < 0).any() and (c["pre"] > 0).any() for c in cache)  # both branches differentiated
+    dx, grads = O.ln_mlp_train_bwd(R, layers, cache, rate, act=act)
+    v = rng.normal(size=x.shape)
+    checks = [("x", _fd(lambda t: f(x_=t), x, v), (dx * v).sum())]
+    for li, p in enumerate(layers):
+        for k in ("W", "b", "gamma", "beta"):
+            v = rng.normal(size=p[k].shape)
+
+            def fp(t, li=li, k=k):
+                ls = [dict(q) for q in layers]
+                ls[li][k] = t
+                return f(layers_=ls)
+
+            checks.append((f"[{li}].{k}", _fd(fp, p[k], v), (grads[li][k] * v).sum()))
+    for name, fd, an in checks:
+        assert abs(fd - an) <= 1e-6 * max(1.0, abs(fd)) + 1e-9, (act, name, fd, an)
+
+
+def test_ln_mlp_train_default_activation_is_gelu():
+    """act defaults to gelu: the same bits with and without the argument, so no earlier caller changes."""
+    rng, x, layers, R = _ln_mlp_case("gelu", 0.3)
+    h0, c0 = O.ln_mlp_train_fwd(x, layers, 0.3, [21, 22])
+    h1, c1 = O.ln_mlp_train_fwd(x, layers, 0.3, [21, 22], act="gelu")
+    assert np.array_equal(h0, h1) and np.array_equal(h0, np.where(c0[1]["keep"], O.gelu(c0[1]["pre"]) / 0.7, 0.0))
+    d0, g0 = O.ln_mlp_train_bwd(R, layers, c0, 0.3)
+    d1, g1 = O.ln_mlp_train_bwd(R, layers, c1, 0.3, act="gelu")
+    assert np.array_equal(d0, d1) and all(np.array_equal(g0[i][k], g1[i][k]) for i in range(2) for k in g0[i])
+    with pytest.raises(ValueError):
+        O.ln_mlp_train_fwd(x, layers, 0.0, [21, 22], act="softmax")
