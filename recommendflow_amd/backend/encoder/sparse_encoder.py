@@ -165,6 +165,8 @@ class FusedSparseEncoder(torch.nn.Module):
         elif table.shape[0] < self.table_rows or table.shape[1] != self.dim:
             raise ValueError(f"shared table {tuple(table.shape)} too small for {self.table_rows} x {self.dim}")
         self.table = table
+        # a backward_plan staged for the next embed backward of `_plan_batch` (stage_plan / take_plan)
+        self._plan = self._plan_batch = self._plan_stream = None
 
     def _single_token_batch(self, batch: SparseBatch) -> bool:
         """True when the batch's per-slot Lmax is known on the host without a device sync and is <= 1, and the
@@ -282,6 +284,20 @@ class FusedSparseEncoder(torch.nn.Module):
                L.ptr(out) if need_mm else None, L.ptr(dout), dout.stride(0), plan.flags, L.ptr(cnt), L.ptr(plan.rows),
                L.ptr(grad), plan.cap, L.ptr(plan.n_uniq), L.ptr(plan.ws), plan.ws.numel(), L.stream_ptr(stream))
         return SparseGrad(plan.rows, grad, plan.n_uniq, plan.cap)
+
+    def stage_plan(self, plan: "BwdPlan", batch: SparseBatch, ready=None):
+        """Hand the embed backward of `batch` (runtime.train.embed) a plan that already ran. `ready`: None when the
+        plan ran on the stream the backward will run on, else the stream it ran on or an event recorded after it."""
+        self._plan, self._plan_batch, self._plan_stream = plan, batch, ready
+
+    def take_plan(self, batch: SparseBatch):
+        """(plan, ready) as staged when the staged batch IS `batch`, and the state cleared; otherwise None and the
+        state left alone."""
+        if self._plan is None or self._plan_batch is not batch:
+            return None
+        staged = (self._plan, self._plan_stream)
+        self._plan = self._plan_batch = self._plan_stream = None
+        return staged
 
     def algorithmic_bytes(self, batch: SparseBatch, pad_rows: bool = False) -> int:
         """HBM bytes one forward must move, SURVEY §8d exactly: bytes = sum_s 2 L_s D e_T (every row occurrence, no

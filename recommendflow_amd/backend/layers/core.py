@@ -9,7 +9,6 @@ BatchNormalization(eps)   tf.keras.layers.BatchNormalization at inference (runni
 from __future__ import annotations
 
 import math
-import os
 from typing import Optional
 
 import torch
@@ -29,20 +28,6 @@ def act_name(activation) -> Optional[str]:
         raise ValueError(f"unsupported activation {activation!r}")
     return name
 
-
-
-# fp32 layers run on rf_gemm_f32 (librf). RF_TOWER_BLASLT_WIDE=1 is an A/B switch only: fp32 layers with K >= 4096
-# then take hipBLASLt (torch.addmm) instead
-_BLASLT_WIDE = os.environ.get("RF_TOWER_BLASLT_WIDE", "0") == "1"
-_BLASLT_MIN_K = int(os.environ.get("RF_TOWER_BLASLT_MIN_K", "4096"))
-
-
-class _nullctx:
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        return False
 
 class Dense(torch.nn.Module):
     def __init__(self, in_features: int, units: int, activation=None, use_bias: bool = True, dtype=torch.bfloat16,
@@ -79,46 +64,7 @@ class Dense(torch.nn.Module):
             x = x.contiguous()
         if out is None:
             out = torch.empty((M, self.units), dtype=torch.float32, device=self.weight.device)
-        return self._linear(x, self.weight, self.bias, out, stream)
-
-    def _linear(self, x, weight, bias, out, stream):
-        """fp32: rf_gemm_f32 (stream-K, bias + activation in the epilogue; hipBLASLt only behind
-        RF_TOWER_BLASLT_WIDE=1). bf16, and fp32 shapes rf_gemm_f32 refuses: rf_linear_fwd, or its split-K form
-        when rf_linear_splitk_ws_bytes > 0 (workspace from the caching allocator on the launch stream)."""
-        M, dt = x.shape[0], L.torch_dtype_code(self.dtype)
-        blaslt = (_BLASLT_WIDE and self.dtype == torch.float32 and self.in_features >= _BLASLT_MIN_K
-                  and out.is_contiguous() and self.activation in (None, "none", "linear", "relu", "selu"))
-        if self.dtype == torch.float32 and not blaslt and self.activation != "softmax" and \
-                G.supported_gemm(x, weight, trans_b=True, out=out):
-            # fp32 layers (the DSSM towers, dssm.py:25-26): rf_gemm_f32, stream-K exact-fp32 MFMA with the bias
-            # and activation in its epilogue
-            return G.gemm_f32(x, weight, trans_b=True, bias=bias, act=self.activation or "none", out=out,
-                              stream=stream)
-        if blaslt:
-            # A/B only: hipBLASLt's fp32 kernel with its bias epilogue, SELU / ReLU in place after
-            G.note_torch_fallback("a Dense layer (RF_TOWER_BLASLT_WIDE=1)")
-            with torch.cuda.stream(stream) if isinstance(stream, torch.cuda.Stream) else _nullctx():
-                if bias is None:
-                    torch.mm(x, weight.t(), out=out)
-                else:
-                    torch.addmm(bias, x, weight.t(), out=out)
-                if self.activation == "selu":
-                    torch.selu_(out)
-                elif self.activation == "relu":
-                    torch.relu_(out)
-            return out
-        ws_bytes = int(L.load().rf_linear_splitk_ws_bytes(dt, M, self.in_features, self.units)) \
-            if self.dtype == torch.float32 else 0
-        if ws_bytes:
-            ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=self.weight.device)
-            L.call("rf_linear_splitk_fwd", L.ptr(x), dt, M, self.in_features, x.stride(0), L.ptr(weight), self.units,
-                   L.ptr(bias), L.ACT[self.activation], L.ptr(out), out.stride(0), L.ptr(ws), ws_bytes,
-                   L.stream_ptr(stream))
-            return out
-        L.call("rf_linear_fwd", L.ptr(x), dt, M, self.in_features, x.stride(0), L.ptr(weight), self.units,
-               L.ptr(bias), L.ACT[self.activation], L.ptr(out), out.stride(0), L.stream_ptr(stream))
-        return out
-
+        return G.linear(x, self.weight, self.bias, self.activation, out, stream)
 
     def forward_with(self, x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor],
                      out: Optional[torch.Tensor] = None, stream=None) -> torch.Tensor:
@@ -131,7 +77,7 @@ class Dense(torch.nn.Module):
         M = x.shape[0]
         if out is None:
             out = torch.empty((M, self.units), dtype=torch.float32, device=self.weight.device)
-        return self._linear(x, weight, bias, out, stream)
+        return G.linear(x, weight, bias, self.activation, out, stream)
 
 
 class LayerNormalization:

@@ -9,15 +9,13 @@ dtype) on the exact-fp32 MFMA path; the sparse part is one fused encoder launch 
 """
 from __future__ import annotations
 
-import os
-from typing import Optional
-
 import torch
 
 from ...backend.blocks.mlp import create_mlp, forward_towers
 from ...backend.encoder.sparse_encoder import FusedSparseEncoder
 from ...backend.layers.core import BatchNormalization
 from ...runtime.batch import SparseBatch
+from ..trainable import SparseTableState
 
 
 class Dssm(torch.nn.Module):
@@ -58,44 +56,6 @@ class Dssm(torch.nn.Module):
         return float(f)
 
 
-class SparseTableState:
-    """What a trainable model over a fused table (self.enc, self.sparse_opt) shares: the table made current, and a
-    state_dict that carries the table with its optimizer's m, v and step count."""
-
-    def materialize(self):
-        """Bring every table row current (deferred Adam) before anything outside step() reads the table."""
-        self.sparse_opt.materialize()
-
-    def embedding_table(self) -> torch.Tensor:
-        """The fused table with every row current: the accessor for readers outside step() / the eval forward
-        (export, search index builds). enc.table itself may hold rows behind by deferred steps."""
-        self.materialize()
-        return self.enc.table
-
-    def _save_to_state_dict(self, destination, prefix, keep_vars):
-        # the fused table is a plain attribute of the encoder, not a parameter: a checkpoint gets it here, with the
-        # table optimizer's m, v and step count, every row current (the dense step's values bit for bit)
-        super()._save_to_state_dict(destination, prefix, keep_vars)
-        st = self.sparse_opt.state()
-        for k in ("table", "m", "v"):
-            t = st[k]
-            destination[prefix + "sparse_" + k] = t if keep_vars else t.detach()
-        destination[prefix + "sparse_iterations"] = torch.tensor(st["iterations"], dtype=torch.int64)
-
-    def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys,
-                              error_msgs):
-        keys = [prefix + "sparse_" + k for k in ("table", "m", "v", "iterations")]
-        present = [k in state_dict for k in keys]
-        if all(present):
-            t, m, v, it = (state_dict[k] for k in keys)
-            # rows loaded are current through the checkpoint's step: the deferred replay starts from there
-            self.sparse_opt.load_state(t, m, v, int(it))
-        elif strict:
-            missing_keys.extend(k for k, p in zip(keys, present) if not p)
-        rest = {k: v for k, v in state_dict.items() if k not in keys}
-        super()._load_from_state_dict(rest, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs)
-
-
 class TrainableDssm(SparseTableState, torch.nn.Module):
     """DSSM training graph (deviation D-dssm-wiring as above): ONE fused encoder over the user slots then
     the ad slots (one forward and one backward launch for both towers), towers
@@ -111,7 +71,6 @@ class TrainableDssm(SparseTableState, torch.nn.Module):
         super().__init__()
         from ...backend.blocks.train_mlp import TrainTower
         from ...backend.losses import match_losses
-        from ...backend.optim import KerasAdam, SparseAdam
 
         self.enc = encoder
         self.wu = 2 * encoder.dim * n_user_slots
@@ -124,17 +83,12 @@ class TrainableDssm(SparseTableState, torch.nn.Module):
                         "inbatch_ce": match_losses.batch_neg_sample_scaled_multi_class_ce_loss}[loss]
         # cosent on the raw tower outputs: normalisation, row dot, loss and their backward in 3 + 4 launches
         self._fused_loss = match_losses.cosine_cosent_loss if loss == "cosent" else None
-        if deferred_adam is None:
-            deferred_adam = self.deferred_table_adam and not lazy_adam
-        self.sparse_opt = SparseAdam(encoder.table, learning_rate=learning_rate, lazy=lazy_adam, deferred=deferred_adam)
-        self.dense_opt = KerasAdam(list(self.user_tower.parameters()) + list(self.ad_tower.parameters()),
-                                   learning_rate=learning_rate)
+        self._init_optimizers(learning_rate, lazy_adam, deferred_adam,
+                              dense_params=list(self.user_tower.parameters()) + list(self.ad_tower.parameters()))
 
-    overlap_table_adam = True  # False: the table's dense Adam runs after the backward in one launch (A/B)
-    # True: the table's dense Adam is deferred per row (SparseAdam(deferred=True): a row's missed untouched steps are
-    # replayed when the row is next read; bit-identical rows, no whole-table pass per step). Default for new models.
-    deferred_table_adam = True
-    fused_loss = os.environ.get("RF_FUSED_LOSS", "1") != "0"  # cosent: match_losses.cosine_cosent_loss on the raw tower outputs (False: torch normalize + loss)
+    # with deferred_adam=False: True splits the table's dense Adam around the backward (step()); False runs it in one
+    # launch after the backward, the unsplit form the split and the deferred ones are tested against
+    overlap_table_adam = True
 
     def _side_stream(self):
         s = getattr(self, "_side", None)
@@ -173,13 +127,8 @@ class TrainableDssm(SparseTableState, torch.nn.Module):
         # single replica, dense (exact Keras) Adam: the table rows NOT in this batch's gradient take their update
         # on a side stream while the towers run (their Keras step needs no gradient); the gradient's rows get
         # theirs after the backward (SparseAdam.apply_untouched / apply_touched == apply, bit for bit)
-        deferred = self.sparse_opt.deferred
-        split = dp is None and not self.sparse_opt.lazy and not deferred and self.overlap_table_adam
-        if deferred:
-            # the batch's rows current before the forward reads them; the backward's reduce reuses the plan
-            plan = self.enc.backward_plan(batch)
-            self.sparse_opt.prepare(plan.rows, plan.n_uniq, plan.cap)
-            self.enc._plan, self.enc._plan_batch, self.enc._plan_stream = plan, batch, None
+        split = dp is None and not self.sparse_opt.lazy and not self.sparse_opt.deferred and self.overlap_table_adam
+        self._stage_rows(batch)
 
         def launch_untouched():
             main = torch.cuda.current_stream()
@@ -198,25 +147,20 @@ class TrainableDssm(SparseTableState, torch.nn.Module):
                     t.record_stream(main)
             # the backward's reduce waits for the plan only: the untouched rows' update keeps running through the
             # towers' backward, the reduce and the touched rows' update (disjoint rows), and the step joins it last
-            self.enc._plan, self.enc._plan_batch, self.enc._plan_stream = plan, batch, planned
+            self.enc.stage_plan(plan, batch, ready=planned)
 
-        fused = self._fused_loss is not None and self.fused_loss
+        fused = self._fused_loss is not None
         u, v = self(batch, after_embed=launch_untouched if split else None, raw=fused)
         loss = self._fused_loss(labels, u, v, eps=1e-6) if fused else self.loss_fn(labels, u, v)
-        from ...backend.blocks.train_mlp import join_input_wgrad, overlap_input_wgrad
-
-        with overlap_input_wgrad():  # the towers' input-layer weight gradients run beside the sparse reduce / Adam
-            (loss * dp.loss_scale() if dp is not None else loss).backward()
+        (loss * dp.loss_scale() if dp is not None else loss).backward()
         sg = self.enc.grad
         if dp is not None:
-            join_input_wgrad()
             dp.allreduce_dense(list(self.user_tower.parameters()) + list(self.ad_tower.parameters()))
             sg = dp.allgather_sparse(sg, self.enc.table_rows)
         if split:
             self.sparse_opt.apply_touched(sg)
         else:
             self.sparse_opt.apply(sg)
-        join_input_wgrad()
         self.dense_opt.step()
         if split:  # the next step's lookup reads every row
             torch.cuda.current_stream().wait_stream(self._side_stream())

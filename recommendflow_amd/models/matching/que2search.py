@@ -20,12 +20,12 @@ from __future__ import annotations
 import torch
 
 from ...runtime.batch import SparseBatch
-from .dssm import SparseTableState
+from ..trainable import TableTrainedModel
 
 MAX_CHANNELS = 16  # rf_attention_fusion_fwd / _bwd: 1 <= channels <= 16
 
 
-class TrainableQue2Search(SparseTableState, torch.nn.Module):
+class TrainableQue2Search(TableTrainedModel):
     """Training and evaluation graph of Que2Search over the sparse channels. `encoder` holds the user slots first,
     then the ad slots; each slot is one channel. step() = forward, backward, SparseAdam on the table (deferred per
     row by default, as TrainableDssm) and KerasAdam on towers, fusions and embedding denses (Keras defaults)."""
@@ -43,7 +43,6 @@ class TrainableQue2Search(SparseTableState, torch.nn.Module):
         from ...backend.blocks.train_mlp import TrainLinear, TrainTower
         from ...backend.layers.fusion_layers import TrainAttentionFusion
         from ...backend.losses import match_losses
-        from ...backend.optim import KerasAdam, SparseAdam
 
         self.enc = encoder
         self.width = 2 * encoder.dim
@@ -60,38 +59,7 @@ class TrainableQue2Search(SparseTableState, torch.nn.Module):
         self.app_dense = TrainLinear(self.dim, self.dim, generator=g, device=dev)
         self.loss_fn = {"cosent": match_losses.cosent_loss,
                         "inbatch_ce": match_losses.batch_neg_sample_scaled_multi_class_ce_loss}[loss]
-        if deferred_adam is None:
-            deferred_adam = not lazy_adam
-        self.sparse_opt = SparseAdam(encoder.table, learning_rate=learning_rate, lazy=lazy_adam, deferred=deferred_adam)
-        self.dense_opt = KerasAdam(list(self.parameters()), learning_rate=learning_rate)
-
-    # ---- checkpoint: the mixin's table / m / v / step count, plus the dense optimizer and the dropout step counters
-    def _save_to_state_dict(self, destination, prefix, keep_vars):
-        super()._save_to_state_dict(destination, prefix, keep_vars)
-        for i, (m, v) in enumerate(zip(self.dense_opt.m, self.dense_opt.v)):
-            destination[f"{prefix}dense_m.{i}"] = m
-            destination[f"{prefix}dense_v.{i}"] = v
-        destination[prefix + "dense_iterations"] = torch.tensor(self.dense_opt.iterations, dtype=torch.int64)
-        destination[prefix + "tower_steps"] = torch.tensor([t.steps for t in self.towers], dtype=torch.int64)
-
-    def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys,
-                              error_msgs):
-        n = len(self.dense_opt.m)
-        keys = [f"{prefix}dense_{k}.{i}" for i in range(n) for k in ("m", "v")]
-        keys += [prefix + "dense_iterations", prefix + "tower_steps"]
-        present = [k in state_dict for k in keys]
-        if all(present):
-            for i in range(n):
-                self.dense_opt.m[i].copy_(state_dict[f"{prefix}dense_m.{i}"])
-                self.dense_opt.v[i].copy_(state_dict[f"{prefix}dense_v.{i}"])
-            self.dense_opt.iterations = int(state_dict[prefix + "dense_iterations"])
-            for t, s in zip(self.towers, state_dict[prefix + "tower_steps"].tolist()):
-                t.steps = int(s)
-        elif strict:
-            missing_keys.extend(k for k, p in zip(keys, present) if not p)
-        drop = set(keys)
-        rest = {k: v for k, v in state_dict.items() if k not in drop}
-        super()._load_from_state_dict(rest, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs)
+        self._init_optimizers(learning_rate, lazy_adam, deferred_adam)
 
     # ---- forward
     def _heads(self, chans):
@@ -121,23 +89,11 @@ class TrainableQue2Search(SparseTableState, torch.nn.Module):
             q, a = self._heads([t(x[:, s * w: (s + 1) * w]) for s, t in enumerate(self.towers)])
         return {"query": q, "app": a}
 
-    def step(self, batch: SparseBatch, labels: torch.Tensor, dp=None) -> torch.Tensor:
-        """One training step on one replica; returns the loss."""
-        if dp is not None:
-            raise NotImplementedError("TrainableQue2Search.step: data-parallel replicas are not implemented")
-        self.train()
-        self.dense_opt.zero_grad(set_to_none=True)
-        if self.sparse_opt.deferred:
-            # the batch's rows current before the forward reads them; the backward's reduce reuses the plan
-            plan = self.enc.backward_plan(batch)
-            self.sparse_opt.prepare(plan.rows, plan.n_uniq, plan.cap)
-            self.enc._plan, self.enc._plan_batch, self.enc._plan_stream = plan, batch, None
-        q, a = self(batch)
-        loss = self.loss_fn(labels, q, a)
-        loss.backward()
-        self.sparse_opt.apply(self.enc.grad)
-        self.dense_opt.step()
-        return loss.detach()
+    def train_towers(self):
+        return list(self.towers)
+
+    def batch_loss(self, batch: SparseBatch, labels: torch.Tensor) -> torch.Tensor:
+        return self.loss_fn(labels, *self(batch))
 
     def get_fusion_weights(self):
         """The batch-averaged attention of each side since init_attention() (que2search.py:152-157)."""

@@ -7,6 +7,7 @@ covers the three layouts:
     weight grad    G  = dpre^T h         gemm_f32(dpre, h, trans_a=True)   A m-contiguous, B n-contiguous
     input grad     dz = dpre W           gemm_f32(dpre, W)                 A k-contiguous, B n-contiguous
 gemm_f32_grouped runs up to 4 such GEMMs of one layout in one launch (the same layer of both towers).
+linear is a Dense layer's forward: rf_gemm_f32 where supported_gemm takes it, else rf_linear_splitk_fwd / rf_linear_fwd.
 The workspace (per-tile counters that every launch leaves zero, then the stream-K partial tiles) is allocated
 zeroed once per (device, stream) and grown as needed; calls on one stream share it.
 """
@@ -105,6 +106,28 @@ def gemm_f32(a: torch.Tensor, b: torch.Tensor, trans_a: bool = False, trans_b: b
     L.call("rf_gemm_f32", L.ptr(A), lda, int(not trans_a), L.ptr(B), ldb, int(trans_b), M, N, K, L.ptr(bias),
            L.ACT[act], L.ptr(out), out.stride(0), L.ptr(ws), ws.numel(), st)
     calls += 1
+    return out
+
+
+def linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], act: Optional[str], out: torch.Tensor,
+           stream=None) -> torch.Tensor:
+    """out = act(x weight^T + bias): a Dense layer's forward, x [M][K] and weight [N][K] of one dtype (fp32 or bf16),
+    fp32 bias. fp32: rf_gemm_f32 (stream-K exact-fp32 MFMA, bias + activation in the epilogue) when supported_gemm
+    takes the operands and the activation is no softmax. Otherwise rf_linear_fwd, or for fp32 its split-K form when
+    rf_linear_splitk_ws_bytes > 0 (workspace from the caching allocator on the launch stream)."""
+    f32 = weight.dtype == torch.float32
+    if f32 and act != "softmax" and supported_gemm(x, weight, trans_b=True, out=out):
+        return gemm_f32(x, weight, trans_b=True, bias=bias, act=act or "none", out=out, stream=stream)
+    (M, K), N, dt = x.shape, weight.shape[0], L.torch_dtype_code(weight.dtype)
+    st = stream if isinstance(stream, int) else L.stream_ptr(stream)
+    ws_bytes = int(L.load().rf_linear_splitk_ws_bytes(dt, M, K, N)) if f32 else 0
+    if ws_bytes:
+        ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=x.device)
+        L.call("rf_linear_splitk_fwd", L.ptr(x), dt, M, K, x.stride(0), L.ptr(weight), N, L.ptr(bias), L.ACT[act],
+               L.ptr(out), out.stride(0), L.ptr(ws), ws_bytes, st)
+    else:
+        L.call("rf_linear_fwd", L.ptr(x), dt, M, K, x.stride(0), L.ptr(weight), N, L.ptr(bias), L.ACT[act], L.ptr(out),
+               out.stride(0), st)
     return out
 
 

@@ -28,17 +28,16 @@ class _EmbedFn(torch.autograd.Function):
     def backward(ctx, dout):
         (out,) = ctx.saved_tensors
         enc = ctx.enc
-        plan = getattr(enc, "_plan", None)
-        if plan is not None and getattr(enc, "_plan_batch", None) is ctx.batch:
-            # the batch-only half already ran (possibly on a side stream: _plan_stream is then that stream or an
-            # event recorded on it after the plan): join it, reduce dout on this stream
-            side = getattr(enc, "_plan_stream", None)
-            if isinstance(side, torch.cuda.Event):
-                torch.cuda.current_stream().wait_event(side)
-            elif side is not None:
-                torch.cuda.current_stream().wait_stream(side)
+        staged = enc.take_plan(ctx.batch)
+        if staged is not None:
+            # the batch-only half already ran (possibly on a side stream: `ready` is then that stream or an event
+            # recorded on it after the plan): join it, reduce dout on this stream
+            plan, ready = staged
+            if isinstance(ready, torch.cuda.Event):
+                torch.cuda.current_stream().wait_event(ready)
+            elif ready is not None:
+                torch.cuda.current_stream().wait_stream(ready)
             enc.grad = enc.backward_reduce(plan, dout.float().contiguous(), out=out)
-            enc._plan = enc._plan_batch = enc._plan_stream = None
         else:
             enc.grad = enc.backward(ctx.batch, dout.float().contiguous(), out=out)
         return None, None, None

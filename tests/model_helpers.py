@@ -17,3 +17,8 @@ def mlp_params(m):
     return [{"W": dn.weight.float().cpu().numpy().T, "b": dn.bias.cpu().numpy(), "gamma": nm.gamma.cpu().numpy(),
              "beta": nm.beta.cpu().numpy(), "mean": None if nm.mean is None else nm.mean.cpu().numpy(),
              "var": None if nm.var is None else nm.var.cpu().numpy()} for nm, dn in zip(m.norms, m.denses)]
+
+
+def state_layout(model):
+    """sorted (key, shape, dtype name) of model.state_dict(): the checkpoint format a literal in a test pins."""
+    return sorted((k, tuple(v.shape), str(v.dtype).replace("torch.", "")) for k, v in model.state_dict().items())

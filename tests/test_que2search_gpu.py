@@ -6,6 +6,7 @@ import pytest
 import torch
 
 import fusion_ref as R
+from model_helpers import state_layout
 from recommendflow_amd.backend.encoder.sparse_encoder import FusedSparseEncoder, SlotSpec
 from recommendflow_amd.models.matching.que2search import TrainableQue2Search
 from recommendflow_amd.runtime import gemm as GM
@@ -152,3 +153,47 @@ def test_step_refuses_data_parallel(cuda):
     model = _model()
     with pytest.raises(NotImplementedError):
         model.step(_batch(8), _labels(8), dp=object())
+
+
+# state_layout() of the tiny model below, written out: a checkpoint written today must still load tomorrow
+Q2S_STATE_LAYOUT = [
+    ('app_dense.W', (8, 8), 'float32'), ('app_dense.b', (8,), 'float32'), ('app_fusion.W', (24, 3), 'float32'),
+    ('app_fusion.infer_weights', (1, 3), 'float32'), ('dense_iterations', (), 'int64'),
+    ('dense_m.0', (8, 8), 'float32'), ('dense_m.1', (8,), 'float32'), ('dense_m.10', (8,), 'float32'),
+    ('dense_m.11', (8,), 'float32'), ('dense_m.12', (8, 8), 'float32'), ('dense_m.13', (8,), 'float32'),
+    ('dense_m.14', (8,), 'float32'), ('dense_m.15', (8,), 'float32'), ('dense_m.16', (8, 1), 'float32'),
+    ('dense_m.17', (24, 3), 'float32'), ('dense_m.18', (8, 8), 'float32'), ('dense_m.19', (8,), 'float32'),
+    ('dense_m.2', (8,), 'float32'), ('dense_m.20', (8, 8), 'float32'), ('dense_m.21', (8,), 'float32'),
+    ('dense_m.3', (8,), 'float32'), ('dense_m.4', (8, 8), 'float32'), ('dense_m.5', (8,), 'float32'),
+    ('dense_m.6', (8,), 'float32'), ('dense_m.7', (8,), 'float32'), ('dense_m.8', (8, 8), 'float32'),
+    ('dense_m.9', (8,), 'float32'), ('dense_v.0', (8, 8), 'float32'), ('dense_v.1', (8,), 'float32'),
+    ('dense_v.10', (8,), 'float32'), ('dense_v.11', (8,), 'float32'), ('dense_v.12', (8, 8), 'float32'),
+    ('dense_v.13', (8,), 'float32'), ('dense_v.14', (8,), 'float32'), ('dense_v.15', (8,), 'float32'),
+    ('dense_v.16', (8, 1), 'float32'), ('dense_v.17', (24, 3), 'float32'), ('dense_v.18', (8, 8), 'float32'),
+    ('dense_v.19', (8,), 'float32'), ('dense_v.2', (8,), 'float32'), ('dense_v.20', (8, 8), 'float32'),
+    ('dense_v.21', (8,), 'float32'), ('dense_v.3', (8,), 'float32'), ('dense_v.4', (8, 8), 'float32'),
+    ('dense_v.5', (8,), 'float32'), ('dense_v.6', (8,), 'float32'), ('dense_v.7', (8,), 'float32'),
+    ('dense_v.8', (8, 8), 'float32'), ('dense_v.9', (8,), 'float32'), ('query_dense.W', (8, 8), 'float32'),
+    ('query_dense.b', (8,), 'float32'), ('query_fusion.W', (8, 1), 'float32'),
+    ('query_fusion.infer_weights', (1, 1), 'float32'), ('sparse_iterations', (), 'int64'),
+    ('sparse_m', (2400, 4), 'float32'), ('sparse_table', (2400, 4), 'float32'), ('sparse_v', (2400, 4), 'float32'),
+    ('tower_steps', (4,), 'int64'), ('towers.0.W.0', (8, 8), 'float32'), ('towers.0.b.0', (8,), 'float32'),
+    ('towers.0.beta.0', (8,), 'float32'), ('towers.0.gamma.0', (8,), 'float32'),
+    ('towers.0.moving_mean_0', (8,), 'float32'), ('towers.0.moving_var_0', (8,), 'float32'),
+    ('towers.1.W.0', (8, 8), 'float32'), ('towers.1.b.0', (8,), 'float32'), ('towers.1.beta.0', (8,), 'float32'),
+    ('towers.1.gamma.0', (8,), 'float32'), ('towers.1.moving_mean_0', (8,), 'float32'),
+    ('towers.1.moving_var_0', (8,), 'float32'), ('towers.2.W.0', (8, 8), 'float32'),
+    ('towers.2.b.0', (8,), 'float32'), ('towers.2.beta.0', (8,), 'float32'), ('towers.2.gamma.0', (8,), 'float32'),
+    ('towers.2.moving_mean_0', (8,), 'float32'), ('towers.2.moving_var_0', (8,), 'float32'),
+    ('towers.3.W.0', (8, 8), 'float32'), ('towers.3.b.0', (8,), 'float32'), ('towers.3.beta.0', (8,), 'float32'),
+    ('towers.3.gamma.0', (8,), 'float32'), ('towers.3.moving_mean_0', (8,), 'float32'),
+    ('towers.3.moving_var_0', (8,), 'float32'),
+]
+
+
+def test_state_dict_layout(cuda):
+    """The checkpoint format: every state_dict() key with its shape and dtype (4 slots x 300 bins, D 4, 1 user slot,
+    dim 8): dense_m / dense_v numbered in list(model.parameters()) order, tower_steps one entry per slot."""
+    specs = [SlotSpec(f"f{s}", 300, (2022, 2023), ["sum", "avg"][s % 2]) for s in range(4)]
+    model = TrainableQue2Search(FusedSparseEncoder(specs, 4, seed=4), 1, 8, dropout=0.3, learning_rate=0.01, seed=3)
+    assert state_layout(model) == Q2S_STATE_LAYOUT

@@ -6,6 +6,7 @@ import pytest
 import torch
 
 import interact_train_ref as T
+from model_helpers import state_layout
 from recommendflow_amd.backend.encoder.sparse_encoder import FusedSparseEncoder, SlotSpec
 from recommendflow_amd.models.ranking.dcn import TrainableDCN
 from recommendflow_amd.models.ranking.deepfm import TrainableDeepFM
@@ -169,3 +170,77 @@ def test_deepfm_first_ids_must_match_the_configuration(cuda):
         _model("deepfm").step(_batch(8), _labels(8), first_ids=torch.zeros(8, 2, dtype=torch.int64, device="cuda"))
     with pytest.raises(ValueError):
         _model("deepfm_first").step(_batch(8), _labels(8))
+
+
+# state_layout() of the tiny models below, written out: a checkpoint written today must still load tomorrow
+STATE_LAYOUT = {
+    "deepfm": [
+        ('dense_iterations', (), 'int64'), ('dense_m.0', (8, 32), 'float32'), ('dense_m.1', (4, 8), 'float32'),
+        ('dense_m.2', (8,), 'float32'), ('dense_m.3', (4,), 'float32'), ('dense_m.4', (32,), 'float32'),
+        ('dense_m.5', (8,), 'float32'), ('dense_m.6', (32,), 'float32'), ('dense_m.7', (8,), 'float32'),
+        ('dense_m.8', (1, 4), 'float32'), ('dense_m.9', (1,), 'float32'), ('dense_v.0', (8, 32), 'float32'),
+        ('dense_v.1', (4, 8), 'float32'), ('dense_v.2', (8,), 'float32'), ('dense_v.3', (4,), 'float32'),
+        ('dense_v.4', (32,), 'float32'), ('dense_v.5', (8,), 'float32'), ('dense_v.6', (32,), 'float32'),
+        ('dense_v.7', (8,), 'float32'), ('dense_v.8', (1, 4), 'float32'), ('dense_v.9', (1,), 'float32'),
+        ('head.W', (1, 4), 'float32'), ('head.b', (1,), 'float32'), ('sparse_iterations', (), 'int64'),
+        ('sparse_m', (2400, 4), 'float32'), ('sparse_table', (2400, 4), 'float32'),
+        ('sparse_v', (2400, 4), 'float32'), ('tower.W.0', (8, 32), 'float32'), ('tower.W.1', (4, 8), 'float32'),
+        ('tower.b.0', (8,), 'float32'), ('tower.b.1', (4,), 'float32'), ('tower.beta.0', (32,), 'float32'),
+        ('tower.beta.1', (8,), 'float32'), ('tower.gamma.0', (32,), 'float32'), ('tower.gamma.1', (8,), 'float32'),
+        ('tower.moving_mean_0', (32,), 'float32'), ('tower.moving_mean_1', (8,), 'float32'),
+        ('tower.moving_var_0', (32,), 'float32'), ('tower.moving_var_1', (8,), 'float32'),
+        ('tower_steps', (1,), 'int64'),
+    ],
+    "deepfm_first": [
+        ('dense_iterations', (), 'int64'), ('dense_m.0', (8, 32), 'float32'), ('dense_m.1', (4, 8), 'float32'),
+        ('dense_m.10', (50, 1), 'float32'), ('dense_m.2', (8,), 'float32'), ('dense_m.3', (4,), 'float32'),
+        ('dense_m.4', (32,), 'float32'), ('dense_m.5', (8,), 'float32'), ('dense_m.6', (32,), 'float32'),
+        ('dense_m.7', (8,), 'float32'), ('dense_m.8', (1, 4), 'float32'), ('dense_m.9', (1,), 'float32'),
+        ('dense_v.0', (8, 32), 'float32'), ('dense_v.1', (4, 8), 'float32'), ('dense_v.10', (50, 1), 'float32'),
+        ('dense_v.2', (8,), 'float32'), ('dense_v.3', (4,), 'float32'), ('dense_v.4', (32,), 'float32'),
+        ('dense_v.5', (8,), 'float32'), ('dense_v.6', (32,), 'float32'), ('dense_v.7', (8,), 'float32'),
+        ('dense_v.8', (1, 4), 'float32'), ('dense_v.9', (1,), 'float32'), ('fm.w', (50, 1), 'float32'),
+        ('head.W', (1, 4), 'float32'), ('head.b', (1,), 'float32'), ('sparse_iterations', (), 'int64'),
+        ('sparse_m', (2400, 4), 'float32'), ('sparse_table', (2400, 4), 'float32'),
+        ('sparse_v', (2400, 4), 'float32'), ('tower.W.0', (8, 32), 'float32'), ('tower.W.1', (4, 8), 'float32'),
+        ('tower.b.0', (8,), 'float32'), ('tower.b.1', (4,), 'float32'), ('tower.beta.0', (32,), 'float32'),
+        ('tower.beta.1', (8,), 'float32'), ('tower.gamma.0', (32,), 'float32'), ('tower.gamma.1', (8,), 'float32'),
+        ('tower.moving_mean_0', (32,), 'float32'), ('tower.moving_mean_1', (8,), 'float32'),
+        ('tower.moving_var_0', (32,), 'float32'), ('tower.moving_var_1', (8,), 'float32'),
+        ('tower_steps', (1,), 'int64'),
+    ],
+    "dcn": [
+        ('cross.b', (3, 32), 'float32'), ('cross.w', (3, 32), 'float32'), ('dense_iterations', (), 'int64'),
+        ('dense_m.0', (8, 32), 'float32'), ('dense_m.1', (4, 8), 'float32'), ('dense_m.10', (1, 36), 'float32'),
+        ('dense_m.11', (1,), 'float32'), ('dense_m.2', (8,), 'float32'), ('dense_m.3', (4,), 'float32'),
+        ('dense_m.4', (32,), 'float32'), ('dense_m.5', (8,), 'float32'), ('dense_m.6', (32,), 'float32'),
+        ('dense_m.7', (8,), 'float32'), ('dense_m.8', (3, 32), 'float32'), ('dense_m.9', (3, 32), 'float32'),
+        ('dense_v.0', (8, 32), 'float32'), ('dense_v.1', (4, 8), 'float32'), ('dense_v.10', (1, 36), 'float32'),
+        ('dense_v.11', (1,), 'float32'), ('dense_v.2', (8,), 'float32'), ('dense_v.3', (4,), 'float32'),
+        ('dense_v.4', (32,), 'float32'), ('dense_v.5', (8,), 'float32'), ('dense_v.6', (32,), 'float32'),
+        ('dense_v.7', (8,), 'float32'), ('dense_v.8', (3, 32), 'float32'), ('dense_v.9', (3, 32), 'float32'),
+        ('head.W', (1, 36), 'float32'), ('head.b', (1,), 'float32'), ('sparse_iterations', (), 'int64'),
+        ('sparse_m', (2400, 4), 'float32'), ('sparse_table', (2400, 4), 'float32'),
+        ('sparse_v', (2400, 4), 'float32'), ('tower.W.0', (8, 32), 'float32'), ('tower.W.1', (4, 8), 'float32'),
+        ('tower.b.0', (8,), 'float32'), ('tower.b.1', (4,), 'float32'), ('tower.beta.0', (32,), 'float32'),
+        ('tower.beta.1', (8,), 'float32'), ('tower.gamma.0', (32,), 'float32'), ('tower.gamma.1', (8,), 'float32'),
+        ('tower.moving_mean_0', (32,), 'float32'), ('tower.moving_mean_1', (8,), 'float32'),
+        ('tower.moving_var_0', (32,), 'float32'), ('tower.moving_var_1', (8,), 'float32'),
+        ('tower_steps', (1,), 'int64'),
+    ],
+}
+
+
+@pytest.mark.parametrize("kind", KINDS)
+def test_state_dict_layout(cuda, kind):
+    """The checkpoint format: every state_dict() key with its shape and dtype (4 slots x 300 bins, D 4, hidden units
+    8 -> 4): dense_m / dense_v numbered in list(model.parameters()) order, tower_steps of shape [1]."""
+    specs = [SlotSpec(f"f{s}", 300, (2022, 2023), ["sum", "avg"][s % 2]) for s in range(4)]
+    enc = FusedSparseEncoder(specs, 4, seed=4)
+    if kind == "dcn":
+        model = TrainableDCN(enc, layer_num=3, hidden_units=(8, 4), dropout=0.3, reg_w=0.01, reg_b=0.02,
+                             learning_rate=0.01, seed=3)
+    else:
+        model = TrainableDeepFM(enc, hidden_units=(8, 4), dropout=0.3, first_order_rows=50 if kind == "deepfm_first" else 0,
+                                w_reg=0.01, learning_rate=0.01, seed=3)
+    assert state_layout(model) == STATE_LAYOUT[kind]

@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 import torch
 
+from model_helpers import state_layout
 from recommendflow_amd.backend.encoder.sparse_encoder import FusedSparseEncoder, SlotSpec
 from recommendflow_amd.models.matching.dssm import TrainableDssm
 from recommendflow_amd.runtime.batch import synthetic_batch
@@ -202,3 +203,28 @@ def test_deferred_adam_checkpoint_round_trip(cuda):
         lf = fresh.step(hbs[k], y)
         assert torch.equal(ld, lf)
     assert torch.equal(fresh.embedding_table(), dense.enc.table)
+
+
+# state_layout() of the tiny model below, written out: a checkpoint written today must still load tomorrow
+DSSM_STATE_LAYOUT = [
+    ('ad_tower.W.0', (8, 16), 'float32'), ('ad_tower.W.1', (4, 8), 'float32'), ('ad_tower.b.0', (8,), 'float32'),
+    ('ad_tower.b.1', (4,), 'float32'), ('ad_tower.beta.0', (16,), 'float32'), ('ad_tower.beta.1', (8,), 'float32'),
+    ('ad_tower.gamma.0', (16,), 'float32'), ('ad_tower.gamma.1', (8,), 'float32'),
+    ('ad_tower.moving_mean_0', (16,), 'float32'), ('ad_tower.moving_mean_1', (8,), 'float32'),
+    ('ad_tower.moving_var_0', (16,), 'float32'), ('ad_tower.moving_var_1', (8,), 'float32'),
+    ('sparse_iterations', (), 'int64'), ('sparse_m', (2400, 4), 'float32'), ('sparse_table', (2400, 4), 'float32'),
+    ('sparse_v', (2400, 4), 'float32'), ('user_tower.W.0', (8, 16), 'float32'), ('user_tower.W.1', (4, 8), 'float32'),
+    ('user_tower.b.0', (8,), 'float32'), ('user_tower.b.1', (4,), 'float32'), ('user_tower.beta.0', (16,), 'float32'),
+    ('user_tower.beta.1', (8,), 'float32'), ('user_tower.gamma.0', (16,), 'float32'),
+    ('user_tower.gamma.1', (8,), 'float32'), ('user_tower.moving_mean_0', (16,), 'float32'),
+    ('user_tower.moving_mean_1', (8,), 'float32'), ('user_tower.moving_var_0', (16,), 'float32'),
+    ('user_tower.moving_var_1', (8,), 'float32'),
+]
+
+
+def test_state_dict_layout(cuda):
+    """The checkpoint format: every state_dict() key with its shape and dtype (4 slots x 300 bins, D 4, 2 user slots,
+    towers 8 -> 4). TrainableDssm carries no dense-optimizer moments and no dropout step counters."""
+    specs = [SlotSpec(f"f{s}", 300, (2022, 2023), ["sum", "avg"][s % 2]) for s in range(4)]
+    model = TrainableDssm(FusedSparseEncoder(specs, 4, seed=4), 2, units=(8, 4), dropout=0.3, learning_rate=0.01, seed=1)
+    assert state_layout(model) == DSSM_STATE_LAYOUT
