@@ -115,6 +115,10 @@ int rf_siphash_bucket(const uint8_t* tok_bytes, const int32_t* tok_off, int64_t 
  *   bag_off[b*n_slots + s] .. bag_off[b*n_slots + s + 1]  token range of (example b, slot s)
  *   tok_off[t] .. tok_off[t+1]                             byte range of token t in tok_bytes
  *   lmax[s]                                                batch max list length of slot s (Lmax_f)
+ * The kernels read a token as the aligned 4-byte words that hold at least one of its bytes, so up to 3 bytes in
+ * front of a token and up to 3 bytes behind it are read as well (never a word without a byte of the token): give
+ * tok_bytes a 4-byte aligned base and an allocation that reaches the end of the last token's word (any hipMalloc'd
+ * buffer does). This holds for every entry point that hashes tok_bytes.
  * d_slots: DEVICE array of n_slots rf_slot_desc, all with .dim == dim.
  * table: fused [table_rows][dim] (table_dtype F32 or BF16).
  * out: [batch][out_stride] (out_dtype F32 or BF16); slot s writes

@@ -142,6 +142,27 @@ __device__ __forceinline__ uint4 row_chunk_src(const TT* __restrict__ table, con
     }
 }
 
+// Both hashes of the token at tok_bytes[tb .. tb + n): the covering aligned dwords are loaded into registers before
+// the rounds (siphash24x2_dev fetches them inside its rounds: one more memory round trip in phase 1's dependent
+// chain bag_off -> tok_off -> message -> hash), as the example-major id kernel does (rf_embed.hip). A token that
+// does not fit the register window takes the streaming form. Same values either way.
+__device__ __forceinline__ void hash_token_x2(const uint8_t* __restrict__ tok_bytes, int tb, int n, uint64_t salt0,
+                                              uint64_t salt1, uint64_t& h0, uint64_t& h1) {
+    const uintptr_t a = reinterpret_cast<uintptr_t>(tok_bytes + tb);
+    const uint32_t sh = (uint32_t)(a & 3);
+    if ((int)sh + n <= 4 * kSipRegWords) {
+        const uint32_t* w = reinterpret_cast<const uint32_t*>(a - sh);
+        const int nw = n > 0 ? (int)((sh + (uint32_t)n + 3) >> 2) : 0;  // only dwords that hold a byte of the token
+        uint32_t wv[kSipRegWords + 1];
+#pragma unroll
+        for (int j = 0; j < kSipRegWords; ++j) wv[j] = j < nw ? w[j] : 0u;
+        wv[kSipRegWords] = 0u;
+        siphash24x2_regs(salt0, salt1, wv, sh, n, h0, h1);
+    } else {
+        siphash24x2_dev(salt0, salt1, tok_bytes + tb, n, h0, h1);
+    }
+}
+
 // Slot-major items: item = (slot s, examples b0 .. b0+kUnits-1). Every unit of an item shares the slot's
 // combiner, Lmax, salts, table segments and pad rows — all wave-uniform (scalar loads, one pad-row
 // prefetch per item) — and unit lengths follow one distribution, so the teams stay balanced.
@@ -313,7 +334,7 @@ __global__ __launch_bounds__(kWaves * 64, fused_min_waves(CPL)) void fused_hash_
             const int t = s_gbeg[wave][lo] + (i - s_loc[wave][lo]);
             const int tb = tok_off[t], n = tok_off[t + 1] - tb;
             uint64_t h0, h1;
-            siphash24x2_dev(salt0, salt1, tok_bytes + tb, n, h0, h1);
+            hash_token_x2(tok_bytes, tb, n, salt0, salt1, h0, h1);
             const int64_t i0 = bucket_from_hash(h0, n, bmod);
             const int64_t i1 = bucket_from_hash(h1, n, bmod);
             if (i < kCap) {
