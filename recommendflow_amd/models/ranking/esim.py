@@ -92,7 +92,8 @@ class Esim(torch.nn.Module):
     # True: the attention gathers its q / a token rows from the tables by id (rf_single_token_ids_fwd ->
     # rf_esim_gather_fwd) when every slot of both batches is single-valued, bf16 tables; the encoders'
     # [B, L, 2D] outputs are then never written. Bit-identical to the encoder path
-    # (test_esim_gather_equals_encoders_plus_attention); cfg3 forward 0.2616 -> 0.1843 ms
+    # (test_esim_gather_equals_encoders_plus_attention at cfg3's shape; per tile count, both widths and in the
+    # persistent loop's steady state in tests/test_esim_gather_gpu.py); cfg3 forward 0.2616 -> 0.1843 ms
     # (profiles/r03/r03b7_cfg3_gather_trace.txt). False: encoders + rf_esim_soft_attention_fwd.
     gather = True
 

@@ -98,7 +98,10 @@ def test_esim_cfg3_shape_vs_oracle(O, cuda):
 def test_esim_gather_equals_encoders_plus_attention(cuda, mask_padding):
     """rf_single_token_ids_fwd -> rf_esim_gather_fwd (the attention gathers its token rows by id) against the
     encoders' [B, L, 2D] outputs -> rf_esim_soft_attention_fwd: the same pooled features and the same forward,
-    bit for bit (100 + 100 single-valued slots, some bags empty: pad rows, or the zero row when masked)."""
+    bit for bit (100 + 100 single-valued slots, some bags empty: pad rows, or the zero row when masked). This is
+    the model-level check at cfg3's shape (d = 128, 7 tiles, one example per workgroup); the kernel-level
+    bit-equality is checked per tile count, both widths and several examples per workgroup, in
+    tests/test_esim_gather_gpu.py."""
     Ls, B = 100, 300
     user = [SlotSpec(f"u{i:03d}", 20_000, (2022, 2023)) for i in range(Ls)]
     ad = [SlotSpec(f"a{i:03d}", 20_000, (2022, 2023)) for i in range(Ls)]
