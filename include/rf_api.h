@@ -977,6 +977,40 @@ size_t rf_cross_bwd_ws_bytes(int32_t batch, int32_t dim, int32_t n_layers);
 int rf_cross_bwd(const void* x, int32_t x_dtype, int64_t ldx, int32_t batch, int32_t dim, int32_t n_layers, const float* w,
                  const float* b, const float* dout, int64_t lddo, float* dx, int64_t lddx, float* dw, float* db, void* ws,
                  size_t ws_bytes, void* stream);
+/*
+ * Backward of rf_cin_fwd; notation as there (Z_k[i][j][d] = X^0[i][d] X^k[j][d]). Activations are recomputed from x:
+ * the forward runs again and leaves X^k, k < K, in the workspace. With dout F32 [batch][sum(sizes)] (row stride lddo,
+ * read in place), for k = K-1 .. 0:
+ *   G^{k+1}[h][d] = dout[b][ooff_k + h] + dX^{k+1}[h][d]                 (the second term for k + 1 < K)
+ *   dW_k[i H_k + j][h] = sum_{b, d} Z_k[b][i][j][d] G^{k+1}[b][h][d]
+ *   dZ_k[i][j][d] = sum_h W_k[i H_k + j][h] G^{k+1}[h][d]                never stored
+ *   dX^k[j][d] = sum_i X^0[i][d] dZ_k[i][j][d],   dX^0[i][d] += sum_j X^k[j][d] dZ_k[i][j][d]
+ * dx: F32, element strides dx_stride_b and dx_stride_f (dx_stride_f >= dim, dx_stride_b >= (fields - 1) dx_stride_f +
+ * dim); only [batch][fields][dim] of the view is written: the launch of layer K-1 writes each element, the launches
+ * of the layers K-2 .. 0 add to it in that order (one stream, so the order is fixed). dW: a HOST array of n_layers
+ * device pointers, dW[k] F32 [fields H_k][H_{k+1}] (the Keras filter layout), overwritten.
+ * packed_w is the forward image (rf_cin_pack_w); packed_w_t is the image of W_k^T that the dZ GEMM reads as its B
+ * operand, written per layer by rf_cin_bwd_pack_w (rf_cin_bwd_packed_w_bytes bytes, 16-byte aligned, all layers).
+ * Precision, the forward's: every MFMA operand is an fp32 value rounded once (RNE) to bf16 (the Z_k products, W_k,
+ * G^{k+1}); accumulation is fp32 on v_mfma_f32_16x16x32_bf16; X^k, G^k and dZ (the accumulators) are carried in fp32;
+ * the contractions of dZ with X^0 and X^k are fp32 multiply-adds on the accumulators; dx and dW are fp32.
+ * Nothing of size [batch][dim][fields H_k] is written. The workspace (rf_cin_bwd_ws_bytes bytes, 16-byte aligned)
+ * holds X^k (k < K) and dX^k (1 <= k < K) in fp32 and one G in bf16, each [H][batch * dim padded], and the dW partials.
+ * Deterministic: no atomics; the contraction over (b, d) runs in chunks of max(1024, rows / 16 rounded up to 32) rows
+ * (rows = 16 * ceil(dim / 16) * batch, padded to 64), whose partials are added in chunk order: the same bits on every
+ * launch. Rows with d >= dim and h, i, j past their sizes contribute exactly zero (G is zeroed there); a NaN in
+ * dout[b] reaches dx[b] and dW only.
+ * Limits as the forward: fields <= 512, sizes[k] <= 512, dim <= 256, 1 <= n_layers <= 8, x F32 or BF16; batch 0 is a
+ * no-op; a shape whose recomputing forward needs more than 160 KiB of LDS is refused as rf_cin_fwd refuses it.
+ */
+size_t rf_cin_bwd_packed_w_bytes(int32_t fields, const int32_t* sizes, int32_t n_layers);
+int rf_cin_bwd_pack_w(const float* W, int32_t layer, int32_t fields, const int32_t* sizes, int32_t n_layers,
+                      void* packed_t, void* stream);
+size_t rf_cin_bwd_ws_bytes(int32_t batch, int32_t fields, int32_t dim, const int32_t* sizes, int32_t n_layers);
+int rf_cin_bwd(const void* x, int32_t x_dtype, int64_t x_stride_b, int64_t x_stride_f, int32_t batch, int32_t fields,
+               int32_t dim, const int32_t* sizes, int32_t n_layers, const void* packed_w, const void* packed_w_t,
+               const float* dout, int64_t lddo, float* dx, int64_t dx_stride_b, int64_t dx_stride_f, float* const* dW,
+               void* ws, size_t ws_bytes, void* stream);
 
 /*
  * Measurement probes (not a reference operator: the ceilings SURVEY §8d states the hot path against).

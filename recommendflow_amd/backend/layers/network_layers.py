@@ -8,10 +8,11 @@ Weights are created on the first call from the input shape, as Keras `build` doe
 tf.random_normal_initializer() are N(0, 0.05^2), w0 starts at zero. FM_Layer, New_FM, CrossNetwork and CIN are the
 inference layers: their parameters do not require gradients and their regularisation coefficients have no effect.
 
-TrainFMLayer, TrainNewFM and TrainCrossNetwork are the same layers under training: the parameters require gradients,
-the forward joins torch autograd through rf_fm_fwd / rf_fm_bwd (the first-order and the gathered gradients reduced per
-id by rf_segment_sum_rows) and rf_cross_fwd / rf_cross_bwd, and regularization() is Keras' l2(c) penalty c * sum(w^2)
-of the weights (w_reg, v_reg, reg_w, reg_b), which a model adds to its loss. CIN has no backward.
+TrainFMLayer, TrainNewFM, TrainCrossNetwork and TrainCIN are the same layers under training: the parameters require
+gradients, the forward joins torch autograd through rf_fm_fwd / rf_fm_bwd (the first-order and the gathered gradients
+reduced per id by rf_segment_sum_rows), rf_cross_fwd / rf_cross_bwd and rf_cin_fwd / rf_cin_bwd, and regularization()
+is Keras' l2(c) penalty c * sum(w^2) of the weights (w_reg, v_reg, reg_w, reg_b, l2_reg), which a model adds to its
+loss.
 """
 from __future__ import annotations
 
@@ -450,3 +451,102 @@ class TrainCrossNetwork(CrossNetwork):
 
     def regularization(self) -> torch.Tensor:
         return _l2(self.reg_w, self.w) + _l2(self.reg_b, self.b)
+
+
+class _CinFn(torch.autograd.Function):
+    """out[:, :sum H] = rf_cin_fwd(x) written through ldo into a [B, sum H + right width] buffer whose right columns
+    take `right` (the concat of xDeepFM); backward = rf_cin_bwd reading its dout in place (lddo). Ws are the layer's
+    master weights (autograd hands their gradients back in the Keras filter shape); the kernels read layer._packed,
+    and the backward packs the transposed image from the master weights."""
+
+    @staticmethod
+    def forward(ctx, x, layer, right, *Ws):
+        B, fields, dim = x.shape
+        K, sumH = len(layer.cin_size), sum(layer.cin_size)
+        extra = 0 if right is None else right.shape[1]
+        lib = L.load()
+        wsb = int(lib.rf_cin_ws_bytes(B, fields, dim, layer._sizes, K))
+        if wsb == 0:
+            L.check(L.RF_EINVAL, "rf_cin_ws_bytes")
+        ws = torch.empty(wsb, dtype=torch.uint8, device=x.device)
+        out = torch.empty((B, sumH + extra), dtype=torch.float32, device=x.device)
+        L.call("rf_cin_fwd", L.ptr(x), L.torch_dtype_code(x.dtype), x.stride(0), x.stride(1), B, fields, dim, layer._sizes, K,
+               L.ptr(layer._packed), L.ptr(out), out.stride(0), L.ptr(ws), ws.numel(), L.stream_ptr())
+        if right is not None:
+            out[:, sumH:] = right
+        ctx.save_for_backward(x)
+        ctx.layer, ctx.packed = layer, layer._packed
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        (x,) = ctx.saved_tensors
+        layer = ctx.layer
+        B, fields, dim = x.shape
+        K, sumH = len(layer.cin_size), sum(layer.cin_size)
+        dout = dout.float()
+        if dout.stride(1) != 1:
+            dout = dout.contiguous()
+        dx = torch.empty((B, fields, dim), dtype=torch.float32, device=x.device)
+        dWs = [torch.empty_like(layer.cin_W['CIN_W_' + str(i)], dtype=torch.float32) for i in range(K)]
+        if B == 0:
+            for d in dWs:
+                d.zero_()
+        lib = L.load()
+        wsb = int(lib.rf_cin_bwd_ws_bytes(B, fields, dim, layer._sizes, K))
+        if wsb == 0:
+            L.check(L.RF_EINVAL, "rf_cin_bwd_ws_bytes")
+        ws = torch.empty(wsb, dtype=torch.uint8, device=x.device)
+        packed_t = layer._pack_transposed()
+        ptrs = (ctypes.c_void_p * K)(*[d.data_ptr() for d in dWs])
+        L.call("rf_cin_bwd", L.ptr(x), L.torch_dtype_code(x.dtype), x.stride(0), x.stride(1), B, fields, dim, layer._sizes, K,
+               L.ptr(ctx.packed), L.ptr(packed_t), L.ptr(dout), dout.stride(0), L.ptr(dx), dx.stride(0), dx.stride(1),
+               ptrs, L.ptr(ws), ws.numel(), L.stream_ptr())
+        if dx.dtype != x.dtype:
+            dx = dx.to(x.dtype)
+        dright = dout[:, sumH:] if ctx.needs_input_grad[2] else None
+        return (dx if ctx.needs_input_grad[0] else None, None, dright, *dWs)
+
+
+class TrainCIN(CIN):
+    """CIN under training: gradients reach the input and every cin_W (rf_cin_bwd; the activations are recomputed, the
+    forward saves x only). forward(x, concat=t) returns [B, sum(cin_size) + t.shape[1]]: the CIN output written
+    straight into the left columns of the concat buffer, t in the right ones.
+
+    The optimizer writes the master weights through raw pointers, which no torch version counter sees, so in
+    training mode the bf16 image is packed from them on every forward (and its transpose in the backward); in eval
+    mode it is packed lazily as CIN does. train() / eval() and load_state_dict drop the cached image."""
+
+    def build(self, input_shape):
+        super().build(input_shape)
+        for p in self.cin_W.values():
+            p.requires_grad_(True)
+
+    def train(self, mode: bool = True):
+        self._packed = None
+        return super().train(mode)
+
+    def _pack_transposed(self) -> torch.Tensor:
+        K = len(self.cin_size)
+        nbytes = int(L.load().rf_cin_bwd_packed_w_bytes(self.embedding_nums, self._sizes, K))
+        if nbytes == 0:
+            L.check(L.RF_EINVAL, "rf_cin_bwd_packed_w_bytes")
+        packed = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        for i in range(K):
+            W = self.cin_W['CIN_W_' + str(i)].data.float().contiguous()
+            L.call("rf_cin_bwd_pack_w", L.ptr(W), i, self.embedding_nums, self._sizes, K, L.ptr(packed), L.stream_ptr())
+        return packed
+
+    def forward(self, inputs: torch.Tensor, concat: Optional[torch.Tensor] = None) -> torch.Tensor:
+        x = _dense_view(inputs)
+        if self.embedding_nums is None:
+            self.build(x.shape)
+        if x.shape[1] != self.embedding_nums:
+            raise ValueError(f"CIN was built for {self.embedding_nums} fields, got {x.shape[1]}")
+        if self.training or self._packed is None:
+            self.refresh()
+        Ws = [self.cin_W['CIN_W_' + str(i)] for i in range(len(self.cin_size))]
+        return _CinFn.apply(x, self, concat, *Ws)
+
+    def regularization(self) -> torch.Tensor:
+        return sum(_l2(self.l2_reg, p) for p in self.cin_W.values())

@@ -3,7 +3,8 @@
 //   rf_cross_fwd  CrossNetwork.call :163-171 (DCN): x_{l+1} = x_0 (x_l . w_l) + b_l + x_l, every layer in one launch
 //   rf_cin_fwd    CIN.call :238-255 (xDeepFM): per layer a GEMM whose A operand (the outer products X0[i,d] X^k[j,d]) is
 //                 generated in registers and never written to HBM
-// and the backward of the two memory-bound ones, rf_fm_bwd and rf_cross_bwd (described at their kernels below).
+// and their backward: rf_fm_bwd and rf_cross_bwd (memory-bound) and rf_cin_bwd (two more generated-operand GEMMs per
+// layer), each described at its kernels below.
 // All are deterministic: no floating-point atomics, every reduction in a fixed order.
 //
 // FM: one wave per example. A lane owns the columns d = lane, lane + 64, ...; the field sum is sequential in f (eight
@@ -703,6 +704,9 @@ struct CinArgs {
     const uint4* wimg;
     float* part;  // [n_sub][sumH]
     CinPlan p;
+    // the stashing forward of rf_cin_bwd (STASH): X^k, k < K, row-minor fp32 [pad16(H_k)][nr] (k = 0: x itself)
+    float* xt[kCinMaxLayers];
+    int64_t nr;
 };
 
 // image of one layer: [k step][tile][lane][8 bf16]; element e of lane l of (ks, tile) is W[k = 32 ks + 8 (l >> 4) + e]
@@ -728,7 +732,7 @@ __global__ __launch_bounds__(256) void cin_pack_kernel(const float* __restrict__
     img[t] = make_uint4(h[0] | (h[1] << 16), h[2] | (h[3] << 16), h[4] | (h[5] << 16), h[6] | (h[7] << 16));
 }
 
-template <int MS, typename T>
+template <int MS, typename T, bool STASH = false>
 __global__ __launch_bounds__(256) void cin_kernel(const CinArgs a) {
     constexpr int MT = MS * 16;           // rows of the workgroup
     constexpr int NW = 4 / MS;            // waves side by side over the output columns
@@ -758,8 +762,11 @@ __global__ __launch_bounds__(256) void cin_kernel(const CinArgs a) {
         const int d = (int)(u - b * p.dsub) * 16 + (m & 15);
         const bool live = u < a.n_sub && d < p.D;
         const T* xp = static_cast<const T*>(a.x) + b * a.sb + d;
-        for (int i = tid / MT; i < p.Hp[0]; i += 256 / MT)
-            x0s[m * p.pitch0 + i] = live && i < p.F0 ? ld_f32(xp + (int64_t)i * a.sf) : 0.f;
+        for (int i = tid / MT; i < p.Hp[0]; i += 256 / MT) {
+            const float v = live && i < p.F0 ? ld_f32(xp + (int64_t)i * a.sf) : 0.f;
+            x0s[m * p.pitch0 + i] = v;
+            if constexpr (STASH) a.xt[0][(int64_t)i * a.nr + u0 * 16 + m] = v;
+        }
     }
     __syncthreads();
 
@@ -853,6 +860,8 @@ __global__ __launch_bounds__(256) void cin_kernel(const CinArgs a) {
                     if (!last) {
 #pragma unroll
                         for (int r = 0; r < 4; ++r) dst[(wm * 16 + 4 * lg + r) * p.pitchX + col] = acc[t][r];
+                        if constexpr (STASH)
+                            *reinterpret_cast<f32x4*>(a.xt[k + 1] + (int64_t)col * a.nr + u * 16 + 4 * lg) = acc[t];
                     }
                     float v = ((acc[t][0] + acc[t][1]) + acc[t][2]) + acc[t][3];
                     v += __shfl_xor(v, 16, 64);
@@ -878,16 +887,387 @@ __global__ __launch_bounds__(256) void cin_reduce_kernel(const float* __restrict
     out[b * ldo + c] = s;
 }
 
-template <int MS, typename T>
+template <int MS, typename T, bool STASH = false>
 int launch_cin(const CinArgs& a, size_t lds, hipStream_t st) {
-    auto kern = cin_kernel<MS, T>;
+    auto kern = cin_kernel<MS, T, STASH>;
     if (lds > 64 * 1024) {
         const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return rf_set_error(RF_EHIP, "rf_cin_fwd: hipFuncSetAttribute: %s", hipGetErrorString(e));
+        if (e != hipSuccess)
+            return rf_set_error(RF_EHIP, "%s: hipFuncSetAttribute: %s", STASH ? "rf_cin_bwd" : "rf_cin_fwd", hipGetErrorString(e));
     }
-    const int64_t grid = (a.n_sub + MS - 1) / MS;
+    // STASH: every subtile of the stash (nr / 16, a multiple of 4) is written, the ones past the batch with zeros
+    const int64_t grid = STASH ? a.nr / 16 / MS : (a.n_sub + MS - 1) / MS;
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), lds, st, a);
     return RF_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// CIN backward
+// ---------------------------------------------------------------------------------------------------------------
+// Rows are the forward's: (example, d) pairs in 16-row subtiles, nr = 16 * (batch * dsub padded to 4) of them. The
+// stashing forward (cin_kernel<.., STASH>) leaves X^k, k < K, in the workspace row-minor, fp32 [h][row]: eight
+// consecutive rows of one h are contiguous, which is what both GEMMs below read. Then for k = K-1 .. 0:
+//   cin_g_kernel     G^{k+1} = dout + dX^{k+1} rounded once to bf16, row-minor [h][row], zero on the padding (d >= D,
+//                    subtiles past the batch, h >= H_{k+1}): those rows add exactly zero to dW and to dx.
+//   cin_dz_kernel    one wave per subtile, MS waves per workgroup. For a field i and 16 consecutive j the dZ tile
+//                    [16 rows][16 j] = G (A operand, bf16 fragments in LDS) x W_k^T (B operand, the image of
+//                    rf_cin_bwd_pack_w read in place) stays in the accumulators; dX^k[row][j] += X0[row][i] acc (in
+//                    registers across the i loop) and dX0[row][i] += sum_j X^k[row][j] acc (a 16-lane DPP tree, then
+//                    added in (j tile) order into the wave's own LDS column). dZ is never written.
+//   cin_dw_kernel    D[m = j][n = h] += sum_rows A[j][row] B[row][h]: a lane's A fragment is X0^T[i][8 rows] times
+//                    X^k^T[j][8 rows], fp32 products rounded once; B is G^T[h][8 rows]. A workgroup owns four fields (one
+//                    per wave), four j tiles and all h, and walks one row chunk; the partial goes to the workspace.
+//   cin_dw_reduce_kernel adds the chunks in order into dW_k and drops the padding.
+// The chunk length depends only on nr: max(1024, nr / 16 rounded up to 32) rows, at most 16 chunks beyond 16384 rows.
+constexpr int kCinDwMinChunk = 1024, kCinDwChunks = 16;
+
+struct CinBwdPlan {
+    int64_t nr;      // rows of every stash (a multiple of 64)
+    int64_t chunk;   // rows per dW chunk (a multiple of 32)
+    int nchunks;
+    int nj[kCinMaxLayers];   // 16-wide j tiles of layer k: ceil(H_k / 16)
+    int nkh[kCinMaxLayers];  // k steps of 32 over h: ceil(H_{k+1} / 32)
+    int64_t wtoff[kCinMaxLayers + 1];  // the layer's transposed image, in uint4
+    size_t part, xt[kCinMaxLayers], dxt[kCinMaxLayers], gt, slab, total;  // byte offsets (dxt[0] unused)
+    size_t slab_elems;  // floats of one chunk's partial: max_k F0 * pad16(H_k) * pad16(H_{k+1})
+};
+
+inline void cin_bwd_images(const CinPlan& p, CinBwdPlan& q) {
+    q.wtoff[0] = 0;
+    for (int k = 0; k < p.K; ++k) {
+        q.nj[k] = (p.H[k] + 15) / 16;
+        q.nkh[k] = (p.H[k + 1] + 31) / 32;
+        q.wtoff[k + 1] = q.wtoff[k] + (int64_t)p.F0 * q.nj[k] * q.nkh[k] * 64;
+    }
+}
+
+inline void cin_bwd_plan(const CinPlan& p, int64_t batch, CinBwdPlan& q) {
+    cin_bwd_images(p, q);
+    const int64_t n_sub = batch * p.dsub;
+    q.nr = std::max<int64_t>((n_sub + 3) / 4 * 4, 4) * 16;
+    q.chunk = std::max<int64_t>(kCinDwMinChunk, ((q.nr + kCinDwChunks - 1) / kCinDwChunks + 31) / 32 * 32);
+    q.nchunks = (int)((q.nr + q.chunk - 1) / q.chunk);
+    size_t off = 0;
+    q.part = off;
+    off += align16((size_t)std::max<int64_t>(n_sub, 1) * p.sumH * sizeof(float));
+    int hn32 = 0;
+    q.slab_elems = 0;
+    for (int k = 0; k < p.K; ++k) {
+        const size_t bytes = (size_t)pad_to(p.H[k], 16) * q.nr * sizeof(float);
+        q.xt[k] = off;
+        off += bytes;
+        q.dxt[k] = off;
+        if (k > 0) off += bytes;
+        hn32 = std::max(hn32, pad_to(p.H[k + 1], 32));
+        q.slab_elems = std::max(q.slab_elems, (size_t)p.F0 * pad_to(p.H[k], 16) * pad_to(p.H[k + 1], 16));
+    }
+    q.gt = off;
+    off += (size_t)hn32 * q.nr * sizeof(uint16_t);
+    q.slab = off;
+    off += (size_t)q.nchunks * q.slab_elems * sizeof(float);
+    q.total = off;
+}
+
+// LDS of one wave of cin_dz_kernel: X0 and dX0 as fp32 [i][16 rows], G as bf16 [16 rows][32 nkh + 8]
+__host__ __device__ inline size_t cin_dz_lds_bytes(int F0, int nkh) { return (size_t)F0 * 16 * 4 * 2 + (size_t)16 * (32 * nkh + 8) * 2; }
+
+// transposed image of one layer: [i][j tile][k step over h][lane][8 bf16]; element e of lane l is
+// W[(i H_k + j)][h] with j = 16 tile + (l & 15), h = 32 ks + 8 (l >> 4) + e, zero where j or h is padding
+__global__ __launch_bounds__(256) void cin_pack_t_kernel(const float* __restrict__ W, int Hk, int Hn, int nj, int nkh,
+                                                         int64_t total, uint4* __restrict__ img) {
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= total) return;
+    const int lane = (int)(t & 63);
+    int64_t q = t >> 6;
+    const int ks = (int)(q % nkh);
+    q /= nkh;
+    const int jt = (int)(q % nj);
+    const int64_t i = q / nj;
+    const int j = jt * 16 + (lane & 15);
+    const int h0 = ks * 32 + 8 * (lane >> 4);
+    uint32_t h[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        const float v = j < Hk && h0 + e < Hn ? W[(i * Hk + j) * Hn + h0 + e] : 0.f;
+        h[e] = f32_to_bf16_bits(v);
+    }
+    img[t] = make_uint4(h[0] | (h[1] << 16), h[2] | (h[3] << 16), h[4] | (h[5] << 16), h[6] | (h[7] << 16));
+}
+
+// gt[h][row .. row + 7] for h < hn32: a thread owns eight consecutive rows (one example) of one h
+__global__ __launch_bounds__(256) void cin_g_kernel(const float* __restrict__ dout, int64_t lddo, int ooff, int Hn, int hn32,
+                                                    const float* __restrict__ dxn, int64_t nr, int64_t n_sub, int dsub,
+                                                    int D, uint4* __restrict__ gt) {
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t n8 = nr / 8;
+    if (t >= n8 * hn32) return;
+    const int h = (int)(t / n8);
+    const int64_t row0 = (t - (int64_t)h * n8) * 8;
+    const int64_t u = row0 / 16;
+    const int64_t b = u / dsub;
+    const int d0 = (int)(u - b * dsub) * 16 + (int)(row0 & 15);
+    uint32_t v[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) v[e] = 0;
+    if (h < Hn && u < n_sub && d0 < D) {
+        const float g = dout[b * lddo + ooff + h];
+        float a[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) a[e] = 0.f;
+        if (dxn) {
+            const float4 a0 = *reinterpret_cast<const float4*>(dxn + (int64_t)h * nr + row0);
+            const float4 a1 = *reinterpret_cast<const float4*>(dxn + (int64_t)h * nr + row0 + 4);
+            a[0] = a0.x, a[1] = a0.y, a[2] = a0.z, a[3] = a0.w;
+            a[4] = a1.x, a[5] = a1.y, a[6] = a1.z, a[7] = a1.w;
+        }
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            if (d0 + e < D) v[e] = f32_to_bf16_bits(g + a[e]);
+        }
+    }
+    gt[t] = make_uint4(v[0] | (v[1] << 16), v[2] | (v[3] << 16), v[4] | (v[5] << 16), v[6] | (v[7] << 16));
+}
+
+struct CinDzArgs {
+    const float* x0t;   // [.][nr]
+    const float* xkt;   // [pad16(H_k)][nr] (layer 0: x0t)
+    const uint16_t* gt;  // [32 nkh][nr]
+    const uint4* wt;    // the layer's transposed image
+    float* dxkt;        // [pad16(H_k)][nr], layers >= 1
+    float* dx;
+    int64_t dsb, dsf, nr, n_sub;
+    int F0, Hk, nj, nkh, dsub, D, layer0, first;
+};
+
+// Sum over each 16-lane row of the wave, in every lane of the row, by DPP (quad_perm [1,0,3,2], quad_perm [2,3,0,1],
+// row_half_mirror, row_mirror): four VALU operations, where a shuffle tree is four LDS round trips.
+template <int CTRL>
+__device__ __forceinline__ float dpp_f(float v) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
+}
+__device__ __forceinline__ float row16_sum(float v) {
+    v += dpp_f<0xB1>(v);
+    v += dpp_f<0x4E>(v);
+    v += dpp_f<0x141>(v);
+    v += dpp_f<0x140>(v);
+    return v;
+}
+
+// NK: the layer's k steps over h (nkh) rounded up to a power of two. The wave's A fragments (G) stay in registers for
+// the whole kernel; the B fragments of UI fields are requested together, so that one trip to L2 is paid per UI fields
+// and not per field (a wave per SIMD hides nothing by itself: the LDS of X0 and dX0 allows no second one).
+template <int NK>
+__global__ __launch_bounds__(256) void cin_dz_kernel(const CinDzArgs a) {
+    constexpr int UI = NK <= 4 ? 8 : 32 / NK;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int lr = lane & 15, lg = lane >> 4;
+    const int F0 = a.F0, nkh = a.nkh, gp = 32 * nkh + 8;  // gp: pitch of G in bf16 (16 bytes past a multiple of 64)
+    char* mine = smem + (size_t)wave * cin_dz_lds_bytes(F0, nkh);
+    float* x0s = reinterpret_cast<float*>(mine);  // [i][16]
+    float* dx0s = x0s + F0 * 16;                   // [i][16]
+    uint16_t* gs = reinterpret_cast<uint16_t*>(dx0s + F0 * 16);  // [16][gp]
+    const int64_t u = (int64_t)blockIdx.x * (blockDim.x >> 6) + wave;  // < nr / 16
+    const int64_t row0 = u * 16;
+
+    for (int q = lane; q < F0 * 16; q += 64) {
+        x0s[q] = a.x0t[(int64_t)(q >> 4) * a.nr + row0 + (q & 15)];
+        dx0s[q] = 0.f;
+    }
+    for (int q = lane; q < 32 * nkh * 16; q += 64) {
+        const int h = q >> 4, m = q & 15;
+        gs[m * gp + h] = a.gt[(int64_t)h * a.nr + row0 + m];
+    }
+    wave_lds_sync();
+
+    // A: G[row lr][h = 32 ks + 8 lg + e]; zero past the layer's k steps (the B fragment there is a repeat)
+    bf16x8 af[NK];
+#pragma unroll
+    for (int ks = 0; ks < NK; ++ks) {
+        uint4 v = make_uint4(0, 0, 0, 0);
+        if (ks < nkh) v = *reinterpret_cast<const uint4*>(gs + lr * gp + 8 * lg + 32 * ks);
+        af[ks] = __builtin_bit_cast(bf16x8, v);
+    }
+    const int64_t istride = (int64_t)a.nj * nkh * 64;  // uint4 per field of the image
+    for (int jt = 0; jt < a.nj; ++jt) {
+        const int j = jt * 16 + lr;
+        f32x4 xk = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (j < a.Hk) xk = *reinterpret_cast<const f32x4*>(a.xkt + (int64_t)j * a.nr + row0 + 4 * lg);
+        f32x4 dxk = f32x4{0.f, 0.f, 0.f, 0.f};
+        const uint4* wb = a.wt + (int64_t)jt * nkh * 64 + lane;
+        for (int i0 = 0; i0 < F0; i0 += UI) {
+            uint4 bw[UI][NK];
+#pragma unroll
+            for (int v = 0; v < UI; ++v) {
+                const uint4* wi = wb + (int64_t)min(i0 + v, F0 - 1) * istride;
+#pragma unroll
+                for (int ks = 0; ks < NK; ++ks) {
+                    const uint4 w = wi[min(ks, nkh - 1) * 64];
+                    bw[v][ks] = ks < nkh ? w : make_uint4(0, 0, 0, 0);
+                }
+            }
+#pragma unroll
+            for (int v = 0; v < UI; ++v) {
+                f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int ks = 0; ks < NK; ++ks)
+                    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[ks], __builtin_bit_cast(bf16x8, bw[v][ks]), acc, 0, 0, 0);
+                // acc: dZ[row 4 lg + r][i, j]
+                const int i = i0 + v;
+                if (i < F0) {
+                    const f32x4 x0v = *reinterpret_cast<const f32x4*>(x0s + i * 16 + 4 * lg);
+                    f32x4 t;
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        dxk[r] += x0v[r] * acc[r];
+                        t[r] = xk[r] * acc[r];
+                    }
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) t[r] = row16_sum(t[r]);
+                    if (lr == 0) {
+                        f32x4* p = reinterpret_cast<f32x4*>(dx0s + i * 16 + 4 * lg);
+                        *p = *p + t;
+                    }
+                }
+            }
+        }
+        if (a.layer0) {
+            // X^0 is both factors: the j side lands in dx too
+            wave_lds_sync();
+            if (j < F0) {
+                f32x4* p = reinterpret_cast<f32x4*>(dx0s + j * 16 + 4 * lg);
+                *p = *p + dxk;
+            }
+            wave_lds_sync();
+        } else {
+            *reinterpret_cast<f32x4*>(a.dxkt + (int64_t)j * a.nr + row0 + 4 * lg) = dxk;
+        }
+    }
+    wave_lds_sync();
+    if (u >= a.n_sub) return;
+    const int64_t b = u / a.dsub;
+    const int dbase = (int)(u - b * a.dsub) * 16;
+    float* dxb = a.dx + b * a.dsb + dbase;
+    for (int q = lane; q < F0 * 16; q += 64) {
+        const int i = q >> 4, m = q & 15;
+        if (dbase + m < a.D) {
+            float* o = dxb + (int64_t)i * a.dsf + m;
+            *o = a.first ? dx0s[q] : *o + dx0s[q];
+        }
+    }
+}
+
+template <int NK>
+int launch_cin_dz(const CinDzArgs& z, int ms, size_t lds, hipStream_t st) {
+    auto kern = cin_dz_kernel<NK>;
+    if (lds > 64 * 1024) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return rf_set_error(RF_EHIP, "rf_cin_bwd: hipFuncSetAttribute: %s", hipGetErrorString(e));
+    }
+    hipLaunchKernelGGL(kern, dim3((unsigned)(z.nr / 16 / ms)), dim3(64 * ms), lds, st, z);
+    return RF_OK;
+}
+
+struct CinDwArgs {
+    const float* x0t;
+    const float* xkt;
+    const uint4* gt;  // bf16 [32 nkh][nr], eight rows per uint4
+    float* slab;      // [nchunks][F0][16 nj][16 nh]
+    int64_t nr, chunk, slab_elems;
+    int F0, Hk, nj, nh, njg;  // nh: 16-wide h tiles; njg: groups of four j tiles
+};
+
+// A workgroup owns four fields (one per wave) and four j tiles; a wave's G fragments of a 32-row step are loaded once
+// and used for its four j tiles (32 MFMAs per 8 + 10 fragment loads), and the waves' G and X^k loads hit the same lines.
+__global__ __launch_bounds__(256) void cin_dw_kernel(const CinDwArgs a) {
+    constexpr int TPW = 8, PJ = 4;
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int lr = lane & 15, lg = lane >> 4;
+    const int i = (blockIdx.x / a.njg) * 4 + wave;
+    const int jt0 = (blockIdx.x % a.njg) * PJ;
+    if (i >= a.F0) return;  // no barrier below
+    const int64_t r0 = (int64_t)blockIdx.y * a.chunk;
+    const int64_t r1 = min(r0 + a.chunk, a.nr);
+    const float* xi = a.x0t + (int64_t)i * a.nr + 8 * lg;
+    const float* xj[PJ];
+    bool jlive[PJ];
+#pragma unroll
+    for (int pj = 0; pj < PJ; ++pj) {
+        const int j = (jt0 + pj) * 16 + lr;
+        jlive[pj] = j < a.Hk;  // also false for a tile past nj
+        xj[pj] = a.xkt + (int64_t)(jlive[pj] ? j : 0) * a.nr + 8 * lg;
+    }
+    const int64_t n8 = a.nr / 8;
+    const int ldo = a.nh * 16;
+    float* out = a.slab + (int64_t)blockIdx.y * a.slab_elems + ((int64_t)i * a.nj + jt0) * 16 * ldo;
+    for (int hp = 0; hp < a.nh; hp += TPW) {
+        f32x4 acc[PJ][TPW];
+#pragma unroll
+        for (int pj = 0; pj < PJ; ++pj) {
+#pragma unroll
+            for (int t = 0; t < TPW; ++t) acc[pj][t] = f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+        for (int64_t row = r0; row < r1; row += 32) {
+            const float4 p0 = *reinterpret_cast<const float4*>(xi + row);
+            const float4 p1 = *reinterpret_cast<const float4*>(xi + row + 4);
+            const uint4* gp = a.gt + (row >> 3) + lg;
+            bf16x8 bfr[TPW];
+#pragma unroll
+            for (int t = 0; t < TPW; ++t) {
+                const int ht = min(hp + t, a.nh - 1);  // past the last tile: a repeat whose accumulator is dropped
+                bfr[t] = __builtin_bit_cast(bf16x8, gp[(int64_t)(ht * 16 + lr) * n8]);
+            }
+#pragma unroll
+            for (int pj = 0; pj < PJ; ++pj) {
+                float4 q0 = *reinterpret_cast<const float4*>(xj[pj] + row);
+                float4 q1 = *reinterpret_cast<const float4*>(xj[pj] + row + 4);
+                if (!jlive[pj]) q0 = q1 = make_float4(0.f, 0.f, 0.f, 0.f);
+                bf16x8 af;
+                af[0] = (__bf16)(p0.x * q0.x);
+                af[1] = (__bf16)(p0.y * q0.y);
+                af[2] = (__bf16)(p0.z * q0.z);
+                af[3] = (__bf16)(p0.w * q0.w);
+                af[4] = (__bf16)(p1.x * q1.x);
+                af[5] = (__bf16)(p1.y * q1.y);
+                af[6] = (__bf16)(p1.z * q1.z);
+                af[7] = (__bf16)(p1.w * q1.w);
+#pragma unroll
+                for (int t = 0; t < TPW; ++t)
+                    acc[pj][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, bfr[t], acc[pj][t], 0, 0, 0);
+            }
+        }
+#pragma unroll
+        for (int pj = 0; pj < PJ; ++pj) {
+            if (jt0 + pj < a.nj) {
+#pragma unroll
+                for (int t = 0; t < TPW; ++t) {
+                    if (hp + t < a.nh) {
+#pragma unroll
+                        for (int r = 0; r < 4; ++r)
+                            out[(pj * 16 + 4 * lg + r) * (int64_t)ldo + (hp + t) * 16 + lr] = acc[pj][t][r];
+                    }
+                }
+            }
+        }
+    }
+}
+
+// dW[(i H_k + j)][h] = the chunks' partials added in chunk order
+__global__ __launch_bounds__(256) void cin_dw_reduce_kernel(const float* __restrict__ slab, int64_t slab_elems, int nchunks,
+                                                            int Hk, int Hn, int nj, int nh, int64_t total,
+                                                            float* __restrict__ dW) {
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= total) return;
+    const int h = (int)(t % Hn);
+    const int64_t ij = t / Hn;
+    const int j = (int)(ij % Hk);
+    const int64_t i = ij / Hk;
+    const float* p = slab + ((i * nj * 16 + j) * (int64_t)(nh * 16)) + h;
+    float s = 0.f;
+    for (int c = 0; c < nchunks; ++c) s += p[(int64_t)c * slab_elems];
+    dW[t] = s;
 }
 
 }  // namespace
@@ -965,7 +1345,7 @@ extern "C" int rf_cin_pack_w(const float* W, int32_t layer, int32_t fields, cons
 extern "C" int rf_cin_fwd(const void* x, int32_t x_dtype, int64_t x_stride_b, int64_t x_stride_f, int32_t batch,
                           int32_t fields, int32_t dim, const int32_t* sizes, int32_t n_layers, const void* packed_w,
                           float* out, int64_t ldo, void* ws, size_t ws_bytes, void* stream) {
-    CinArgs a;
+    CinArgs a{};
     if (!cin_plan(fields, dim, sizes, n_layers, a.p, "rf_cin_fwd")) return RF_EINVAL;
     RF_REQUIRE(batch >= 0, "rf_cin_fwd: batch must be >= 0");
     RF_REQUIRE(x_dtype == RF_DTYPE_F32 || x_dtype == RF_DTYPE_BF16, "rf_cin_fwd: x_dtype must be F32 or BF16");
@@ -1050,4 +1430,147 @@ extern "C" int rf_cross_bwd(const void* x, int32_t x_dtype, int64_t ldx, int32_t
     else
         dispatch_cross_bwd<uint16_t>(x, ldx, batch, dim, n_layers, w, b, dout, lddo, dx, lddx, dw, db, static_cast<char*>(ws), lay, st);
     return rf_check_launch("rf_cross_bwd");
+}
+
+extern "C" size_t rf_cin_bwd_packed_w_bytes(int32_t fields, const int32_t* sizes, int32_t n_layers) {
+    CinPlan p;
+    if (!cin_plan(fields, 1, sizes, n_layers, p, "rf_cin_bwd_packed_w_bytes")) return 0;
+    CinBwdPlan q;
+    cin_bwd_images(p, q);
+    return (size_t)q.wtoff[n_layers] * sizeof(uint4);
+}
+
+extern "C" size_t rf_cin_bwd_ws_bytes(int32_t batch, int32_t fields, int32_t dim, const int32_t* sizes, int32_t n_layers) {
+    CinPlan p;
+    if (batch < 0 || !cin_plan(fields, dim, sizes, n_layers, p, "rf_cin_bwd_ws_bytes")) return 0;
+    CinBwdPlan q;
+    cin_bwd_plan(p, batch, q);
+    return q.total;
+}
+
+extern "C" int rf_cin_bwd_pack_w(const float* W, int32_t layer, int32_t fields, const int32_t* sizes, int32_t n_layers,
+                                 void* packed_t, void* stream) {
+    CinPlan p;
+    if (!cin_plan(fields, 1, sizes, n_layers, p, "rf_cin_bwd_pack_w")) return RF_EINVAL;
+    RF_REQUIRE(layer >= 0 && layer < n_layers, "rf_cin_bwd_pack_w: layer (%d) must be in [0, %d)", layer, n_layers);
+    RF_REQUIRE(W && packed_t && ((uintptr_t)packed_t & 15) == 0,
+               "rf_cin_bwd_pack_w: null pointer or packed_t not 16-byte aligned");
+    CinBwdPlan q;
+    cin_bwd_images(p, q);
+    const int64_t total = q.wtoff[layer + 1] - q.wtoff[layer];
+    hipLaunchKernelGGL(cin_pack_t_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, rf_stream(stream), W,
+                       p.H[layer], p.H[layer + 1], q.nj[layer], q.nkh[layer], total,
+                       static_cast<uint4*>(packed_t) + q.wtoff[layer]);
+    return rf_check_launch("rf_cin_bwd_pack_w");
+}
+
+extern "C" int rf_cin_bwd(const void* x, int32_t x_dtype, int64_t x_stride_b, int64_t x_stride_f, int32_t batch,
+                          int32_t fields, int32_t dim, const int32_t* sizes, int32_t n_layers, const void* packed_w,
+                          const void* packed_w_t, const float* dout, int64_t lddo, float* dx, int64_t dx_stride_b,
+                          int64_t dx_stride_f, float* const* dW, void* ws, size_t ws_bytes, void* stream) {
+    CinArgs a{};
+    if (!cin_plan(fields, dim, sizes, n_layers, a.p, "rf_cin_bwd")) return RF_EINVAL;
+    const CinPlan& p = a.p;
+    RF_REQUIRE(batch >= 0, "rf_cin_bwd: batch must be >= 0");
+    RF_REQUIRE(x_dtype == RF_DTYPE_F32 || x_dtype == RF_DTYPE_BF16, "rf_cin_bwd: x_dtype must be F32 or BF16");
+    RF_REQUIRE(x_stride_f >= dim && x_stride_b >= 0, "rf_cin_bwd: x_stride_f must be >= dim");
+    RF_REQUIRE(lddo >= p.sumH, "rf_cin_bwd: lddo must be >= sum(sizes)");
+    RF_REQUIRE(dx_stride_f >= dim && dx_stride_b >= (int64_t)(fields - 1) * dx_stride_f + dim,
+               "rf_cin_bwd: dx_stride_f must be >= dim and dx_stride_b >= (fields - 1) * dx_stride_f + dim");
+    if (batch == 0) return RF_OK;
+    RF_REQUIRE(x && packed_w && packed_w_t && dout && dx && dW, "rf_cin_bwd: null pointer");
+    for (int k = 0; k < n_layers; ++k) RF_REQUIRE(dW[k], "rf_cin_bwd: dW[%d] is null", k);
+    RF_REQUIRE(((uintptr_t)packed_w & 15) == 0, "rf_cin_bwd: packed_w must be 16-byte aligned");
+    RF_REQUIRE(((uintptr_t)packed_w_t & 15) == 0, "rf_cin_bwd: packed_w_t must be 16-byte aligned");
+    RF_REQUIRE(ws && ((uintptr_t)ws & 15) == 0, "rf_cin_bwd: null or misaligned workspace");
+    CinBwdPlan q;
+    cin_bwd_plan(p, batch, q);
+    RF_REQUIRE(ws_bytes >= q.total, "rf_cin_bwd: ws_bytes too small (%zu < %zu)", ws_bytes, q.total);
+    RF_REQUIRE(q.nr < ((int64_t)1 << 31), "rf_cin_bwd: batch * dim too large");
+    int ms = 4;
+    while (ms > 1 && cin_lds_bytes(p, ms) > 160 * 1024) ms >>= 1;
+    const size_t lds = cin_lds_bytes(p, ms);
+    RF_REQUIRE(lds <= 160 * 1024, "rf_cin_bwd: the recomputing forward needs %zu bytes of LDS (> 160 KiB)", lds);
+    int zms[kCinMaxLayers];
+    for (int k = 0; k < n_layers; ++k) {
+        zms[k] = 4;
+        while (zms[k] > 1 && zms[k] * cin_dz_lds_bytes(p.F0, q.nkh[k]) > 160 * 1024) zms[k] >>= 1;
+        const size_t need = zms[k] * cin_dz_lds_bytes(p.F0, q.nkh[k]);
+        RF_REQUIRE(need <= 160 * 1024, "rf_cin_bwd: layer %d needs %zu bytes of LDS (> 160 KiB)", k, need);
+    }
+    char* w8 = static_cast<char*>(ws);
+    hipStream_t st = rf_stream(stream);
+
+    // the forward again, X^k (k < K) to the workspace
+    a.x = x;
+    a.sb = x_stride_b;
+    a.sf = x_stride_f;
+    a.n_sub = (int64_t)batch * p.dsub;
+    a.wimg = static_cast<const uint4*>(packed_w);
+    a.part = reinterpret_cast<float*>(w8 + q.part);
+    a.nr = q.nr;
+    for (int k = 0; k < n_layers; ++k) a.xt[k] = reinterpret_cast<float*>(w8 + q.xt[k]);
+    const bool f32 = x_dtype == RF_DTYPE_F32;
+    int rc;
+    if (ms == 4) rc = f32 ? launch_cin<4, float, true>(a, lds, st) : launch_cin<4, uint16_t, true>(a, lds, st);
+    else if (ms == 2) rc = f32 ? launch_cin<2, float, true>(a, lds, st) : launch_cin<2, uint16_t, true>(a, lds, st);
+    else rc = f32 ? launch_cin<1, float, true>(a, lds, st) : launch_cin<1, uint16_t, true>(a, lds, st);
+    if (rc != RF_OK) return rc;
+
+    uint4* gt = reinterpret_cast<uint4*>(w8 + q.gt);
+    float* slab = reinterpret_cast<float*>(w8 + q.slab);
+    for (int k = n_layers - 1; k >= 0; --k) {
+        const int Hk = p.H[k], Hn = p.H[k + 1], hn32 = 32 * q.nkh[k];
+        const float* dxn = k + 1 < n_layers ? reinterpret_cast<const float*>(w8 + q.dxt[k + 1]) : nullptr;
+        const int64_t gtotal = q.nr / 8 * hn32;
+        hipLaunchKernelGGL(cin_g_kernel, dim3((unsigned)((gtotal + 255) / 256)), dim3(256), 0, st, dout, lddo, p.ooff[k], Hn,
+                           hn32, dxn, q.nr, a.n_sub, p.dsub, p.D, gt);
+
+        CinDzArgs z;
+        z.x0t = a.xt[0];
+        z.xkt = a.xt[k];
+        z.gt = reinterpret_cast<const uint16_t*>(gt);
+        z.wt = static_cast<const uint4*>(packed_w_t) + q.wtoff[k];
+        z.dxkt = k > 0 ? reinterpret_cast<float*>(w8 + q.dxt[k]) : nullptr;
+        z.dx = dx;
+        z.dsb = dx_stride_b;
+        z.dsf = dx_stride_f;
+        z.nr = q.nr;
+        z.n_sub = a.n_sub;
+        z.F0 = p.F0;
+        z.Hk = Hk;
+        z.nj = q.nj[k];
+        z.nkh = q.nkh[k];
+        z.dsub = p.dsub;
+        z.D = p.D;
+        z.layer0 = k == 0;
+        z.first = k == n_layers - 1;
+        const size_t zlds = zms[k] * cin_dz_lds_bytes(p.F0, q.nkh[k]);
+        int rcz;
+        if (z.nkh <= 1) rcz = launch_cin_dz<1>(z, zms[k], zlds, st);
+        else if (z.nkh <= 2) rcz = launch_cin_dz<2>(z, zms[k], zlds, st);
+        else if (z.nkh <= 4) rcz = launch_cin_dz<4>(z, zms[k], zlds, st);
+        else if (z.nkh <= 8) rcz = launch_cin_dz<8>(z, zms[k], zlds, st);
+        else rcz = launch_cin_dz<16>(z, zms[k], zlds, st);
+        if (rcz != RF_OK) return rcz;
+
+        CinDwArgs w;
+        w.x0t = a.xt[0];
+        w.xkt = a.xt[k];
+        w.gt = gt;
+        w.slab = slab;
+        w.nr = q.nr;
+        w.chunk = q.chunk;
+        w.slab_elems = (int64_t)q.slab_elems;
+        w.Hk = Hk;
+        w.nj = q.nj[k];
+        w.nh = (Hn + 15) / 16;
+        w.F0 = p.F0;
+        w.njg = (w.nj + 3) / 4;
+        hipLaunchKernelGGL(cin_dw_kernel, dim3((unsigned)((p.F0 + 3) / 4 * w.njg), (unsigned)q.nchunks), dim3(256), 0, st, w);
+        const int64_t total = (int64_t)p.F0 * Hk * Hn;
+        hipLaunchKernelGGL(cin_dw_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, slab,
+                           (int64_t)q.slab_elems, q.nchunks, Hk, Hn, w.nj, w.nh, total, dW[k]);
+    }
+    return rf_check_launch("rf_cin_bwd");
 }

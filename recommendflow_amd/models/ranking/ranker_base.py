@@ -1,4 +1,4 @@
-"""What the trainable rankers over the fused encoder (DeepFM, DCN) add to models.trainable.TableTrainedModel: ONE fused
+"""What the trainable rankers over the fused encoder (DeepFM, DCN, xDeepFM) add to models.trainable.TableTrainedModel: ONE fused
 encoder through runtime.train.embed, the logits of a batch, sigmoid cross-entropy plus the layers' l2 penalties."""
 from __future__ import annotations
 

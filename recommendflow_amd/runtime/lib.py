@@ -161,6 +161,11 @@ _SIGS = {
     "rf_cross_bwd_ws_bytes": (ctypes.c_size_t, [_i32, _i32, _i32]),
     "rf_cross_bwd": (ctypes.c_int, [_vp, _i32, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp,
                                     ctypes.c_size_t, _vp]),
+    "rf_cin_bwd_packed_w_bytes": (ctypes.c_size_t, [_i32, _vp, _i32]),
+    "rf_cin_bwd_pack_w": (ctypes.c_int, [_vp, _i32, _i32, _vp, _i32, _vp, _vp]),
+    "rf_cin_bwd_ws_bytes": (ctypes.c_size_t, [_i32, _i32, _i32, _vp, _i32]),
+    "rf_cin_bwd": (ctypes.c_int, [_vp, _i32, _i64, _i64, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _i64, _vp, _i64, _i64,
+                                  _vp, _vp, ctypes.c_size_t, _vp]),
 }
 EXPORTED = tuple(_SIGS)
 # include/rf_diag.h: tools-only entry points (not the production ABI)

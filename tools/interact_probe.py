@@ -19,9 +19,15 @@ the same run's copy rate:
   steps      one step() of TrainableDeepFM and TrainableDCN: B 4096, 32 slots x D 64 (a [4096, 4096] embed output),
              250k bins per slot, hidden units (256, 128), DCN with 3 cross layers
 
+CIN training leg (--legs cin_train only; written to --cin-train-out, default profiles/interact/cin_train_probe.json):
+  cin_bwd    rf_cin_bwd at the forward leg's shape (B 4096, 200 fields x 128 dims bf16, cin_size [128, 128]; it runs the
+             forward again), rf_cin_fwd beside it, and torch autograd (forward + backward) through the forward leg's
+             bf16 composition in batch chunks, in the same process; --no-torch skips the composition
+  step       one step() of TrainableXDeepFM at the step shape above (32 slots x D 64: CIN over [4096, 32, 128])
+
 Timing: HIP events around `reps` back-to-back calls after `warm` warm-up calls; ms per call. Writes the JSON (default
 profiles/interact/interact_probe.json).
-    python tools/interact_probe.py [--out PATH] [--batch B] [--legs forward|train|all]"""
+    python tools/interact_probe.py [--out PATH] [--batch B] [--legs forward|train|all|cin_train]"""
 import argparse
 import json
 import os
@@ -38,7 +44,9 @@ from recommendflow_amd.runtime import lib as L  # noqa: E402
 ap = argparse.ArgumentParser()
 ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "interact", "interact_probe.json"))
 ap.add_argument("--train-out", default=os.path.join(ROOT, "profiles", "interact", "interact_train_probe.json"))
-ap.add_argument("--legs", choices=["forward", "train", "all"], default="all")
+ap.add_argument("--cin-train-out", default=os.path.join(ROOT, "profiles", "interact", "cin_train_probe.json"))
+ap.add_argument("--legs", choices=["forward", "train", "all", "cin_train"], default="all")
+ap.add_argument("--no-torch", action="store_true", help="cin_train: skip the torch autograd composition")
 ap.add_argument("--step-reps", type=int, default=20)
 ap.add_argument("--batch", type=int, default=4096)
 ap.add_argument("--reps", type=int, default=20)
@@ -238,6 +246,109 @@ def train_legs():
     print(json.dumps(out))
 
 
+def cin_train_leg():
+    import ctypes
+
+    from recommendflow_amd.backend.encoder.sparse_encoder import FusedSparseEncoder, SlotSpec
+    from recommendflow_amd.models.ranking import TrainableXDeepFM
+    from recommendflow_amd.runtime.batch import synthetic_batch
+
+    out = {"batch": B, "device": res["device"], "stream_copy_GBs": res["stream_copy_GBs"]}
+    F0, D, sizes = 200, 128, [128, 128]
+    K, sumH = len(sizes), sum(sizes)
+    x = (torch.rand((B, F0, D), device="cuda", generator=g) * 2 - 1).to(torch.bfloat16)
+    cin = N.TrainCIN(sizes, seed=2)
+    cin.build(x.shape)
+    Hk = F0
+    for i, H in enumerate(sizes):
+        cin.cin_W[f"CIN_W_{i}"].data.copy_(torch.randn((1, F0 * Hk, H), device="cuda", generator=g) / (F0 * Hk) ** 0.5)
+        Hk = H
+    cin.refresh()
+    packed, packed_t = cin._packed, cin._pack_transposed()
+    dout = torch.randn((B, sumH), device="cuda", generator=g)
+    lib = L.load()
+    wsb = int(lib.rf_cin_bwd_ws_bytes(B, F0, D, cin._sizes, K))
+    ws = torch.empty(wsb, dtype=torch.uint8, device="cuda")
+    dx = torch.empty((B, F0, D), dtype=torch.float32, device="cuda")
+    dWs = [torch.empty_like(cin.cin_W[f"CIN_W_{i}"].data) for i in range(K)]
+    ptrs = (ctypes.c_void_p * K)(*[d.data_ptr() for d in dWs])
+
+    def bwd():
+        L.call("rf_cin_bwd", L.ptr(x), L.DT_BF16, x.stride(0), x.stride(1), B, F0, D, cin._sizes, K, L.ptr(packed),
+               L.ptr(packed_t), L.ptr(dout), dout.stride(0), L.ptr(dx), dx.stride(0), dx.stride(1), ptrs, L.ptr(ws), wsb, st)
+
+    with torch.no_grad():
+        fwd_ms = ev(lambda: cin(x), args.cin_reps, 1)
+    bwd_ms = ev(bwd, args.cin_reps, 1)
+    flops, Hk = 0, F0
+    for H in sizes:
+        flops += 2 * B * D * F0 * Hk * H
+        Hk = H
+    leg = {"shape": [B, F0, D], "cin_size": sizes, "x_dtype": "bf16", "forward_flops": flops, "backward_flops": 3 * flops,
+           "ws_bytes": wsb, "packed_w_bytes": packed.numel(), "packed_w_t_bytes": packed_t.numel(),
+           "rf_cin_fwd_ms": round(fwd_ms, 3), "rf_cin_bwd_ms": round(bwd_ms, 3),
+           "rf_cin_bwd_TFLOPs": round(3 * flops / bwd_ms / 1e9, 1),
+           "bwd_over_fwd": round(bwd_ms / fwd_ms, 2), "bwd_over_3x_design_fwd_33.4ms": round(bwd_ms / (3 * 33.4), 2)}
+    if not args.no_torch:
+        Wl = [cin.cin_W[f"CIN_W_{i}"].data[0].to(torch.bfloat16).requires_grad_(True) for i in range(K)]
+
+        def composed(xc):
+            b = xc.shape[0]
+            x0 = xc.permute(0, 2, 1)
+            xk, outs = x0.float(), []
+            for W in Wl:
+                outer = (x0.unsqueeze(3) * xk.to(torch.bfloat16).unsqueeze(2)).reshape(b * D, -1)
+                xk = torch.matmul(outer, W).float().view(b, D, -1)
+                outs.append(xk.sum(dim=1))
+            return torch.cat(outs, dim=1)
+
+        def torch_train():
+            """forward + backward per batch chunk: dx per chunk, the dW of the chunks accumulated by autograd"""
+            for W in Wl:
+                W.grad = None
+            dxs = []
+            for i in range(0, B, args.chunk):
+                xc = x[i: i + args.chunk].detach().requires_grad_(True)
+                (composed(xc) * dout[i: i + args.chunk]).sum().backward()
+                dxs.append(xc.grad)
+            return torch.cat(dxs, dim=0)
+
+        def torch_fwd():
+            with torch.no_grad():
+                return [composed(x[i: i + args.chunk]) for i in range(0, B, args.chunk)]
+
+        tf_ms = ev(torch_fwd, 1, 1)
+        tt_ms = ev(torch_train, 1, 1)
+        want = torch_train()
+        bwd()
+        leg.update({"torch_chunk": args.chunk, "torch_forward_ms": round(tf_ms, 3),
+                    "torch_forward_backward_ms": round(tt_ms, 3), "torch_backward_ms": round(tt_ms - tf_ms, 3),
+                    "speedup_fwd_plus_bwd_over_torch": round(tt_ms / (fwd_ms + bwd_ms), 2),
+                    "speedup_bwd_over_torch_backward": round((tt_ms - tf_ms) / bwd_ms, 2),
+                    "dx_rel_diff_vs_torch": float((dx - want.float()).abs().max() / want.float().abs().max()),
+                    "dW_rel_diff_vs_torch": [float((dWs[i][0] - Wl[i].grad.float()).abs().max() /
+                                                   Wl[i].grad.float().abs().max()) for i in range(K)]})
+        del Wl, want
+    out["cin_bwd"] = leg
+    del x, dx, ws, dout, dWs
+    SL, DD, BINS = 32, 64, 250_000
+    hb = synthetic_batch(B, [s % 2 == 1 for s in range(SL)], seed=3).to("cuda")
+    yl = (torch.arange(B, device="cuda") % 2).float()
+    specs = [SlotSpec(f"f{s}", BINS, (2022, 2023), ["sum", "avg"][s % 2]) for s in range(SL)]
+    enc = FusedSparseEncoder(specs, DD, seed=4)
+    model = TrainableXDeepFM(enc, seed=1)
+    ms = ev(lambda: model.step(hb, yl), args.step_reps, 5)
+    out["step"] = {"B": B, "slots": SL, "D": DD, "embed_width": SL * 2 * DD, "table_rows": enc.table_rows,
+                   "hidden_units": [256, 128], "cin_size": [128, 128], "step_ms": round(ms, 3)}
+    os.makedirs(os.path.dirname(os.path.abspath(args.cin_train_out)), exist_ok=True)
+    with open(args.cin_train_out, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    print(json.dumps(out))
+
+
+if args.legs == "cin_train":
+    cin_train_leg()
 if args.legs in ("forward", "all"):
     forward_legs()
 if args.legs in ("train", "all"):
