@@ -1012,6 +1012,48 @@ int rf_cin_bwd(const void* x, int32_t x_dtype, int64_t x_stride_b, int64_t x_str
                const float* dout, int64_t lddo, float* dx, int64_t dx_stride_b, int64_t dx_stride_f, float* const* dW,
                void* ws, size_t ws_bytes, void* stream);
 
+/* ---- TransformerEncoder over the fields, forward (rf_tfenc.hip) ------------------------------------------- */
+/*
+ * A stack of n_blocks TransformerEncoder blocks (network_layers.py:319-352) in one launch. Per block, with x [L][d_model]
+ * of one example, depth = d_model / heads and head h owning the columns [h depth, (h + 1) depth):
+ *   q = x Wq + bq, k = x Wk + bk, v = x Wv + bv              (MultiHeadAttention.call, attention_layers.py:153-168; no
+ *                                                              output projection)
+ *   logits = q_h k_h^T / sqrt(depth); logits[i][:] = -4294967295 where mask[b][i] == 0        (layer_utils.py:13-19)
+ *   att = softmax_over_keys(logits) v_h, heads merged to [L][d_model]
+ *   out1 = LayerNorm(x + att; gamma1, beta1)                                                   (:343-346)
+ *   x'   = LayerNorm(out1 + relu(out1 W1 + b1) W2 + b2; gamma2, beta2)                         (FFN :310-316, :348-351)
+ * Both dropouts are the identity. The mask marks QUERY rows and broadcasts over the keys: a masked row gets a uniform
+ * softmax, its attention output is the mean of v over all L keys (masked rows' keys included). mask: F32 [batch][L],
+ * NULL = no mask (as rf_sdpa_fwd). eps: one float for every LayerNorm (biased variance, as Keras).
+ * x: F32 or BF16, d contiguous, element strides x_stride_b, x_stride_l. out: F32, element strides out_stride_b,
+ * out_stride_l (out_stride_l >= d_model, out_stride_b >= (L - 1) out_stride_l + d_model); only [batch][L][d_model] of the
+ * view is written. The activations between the blocks, and x + att inside a block, pass through out and nothing else
+ * of size [batch][L][.] exists. batch 0 is a no-op.
+ * Weights: rf_tfenc_pack builds block `block` of the kernel image on the device (rf_tfenc_packed_bytes bytes, 16-byte
+ * aligned, all blocks) from the fp32 masters in Keras layouts: Wq, Wk, Wv [d_model][d_model] and W1 [d_model][ffn_hidden]
+ * as (in, out), W2 [ffn_hidden][d_model]; the matrices as bf16 MFMA fragments (one 16-byte read each), the biases and
+ * the LayerNorm parameters in fp32.
+ * Precision: every MFMA operand is an fp32 value rounded once (RNE) to bf16: x, the weights, q, k, v after the bias,
+ * the softmax probabilities, out1 as the FFN's input and relu(.) as W2's input; accumulation is fp32 on
+ * v_mfma_f32_16x16x32_bf16. The scale, the mask replacement and the softmax (max subtracted), the residual stream (x,
+ * x + att, out1 + ffn), the LayerNorm statistics and out are fp32. Deterministic: no atomics, fixed reduction orders,
+ * the same bits on every launch.
+ * Limits: 1 <= L <= 256 (padded inside the kernel; a padded key never enters a softmax); d_model a multiple of 16 in
+ * [16, 256]; heads divides d_model and depth is a multiple of 16; ffn_hidden a multiple of 16 in [16, 1024];
+ * 1 <= n_blocks <= 8. The example's K and V stay in LDS in bf16 (rf_tfenc_lds_bytes; 0 with the error set for a refused
+ * shape): a shape that needs more than 160 KiB is refused as rf_cin_fwd refuses it ((L 256, d_model 128) and
+ * (L 128, d_model 256) fit).
+ */
+size_t rf_tfenc_packed_bytes(int32_t d_model, int32_t ffn_hidden, int32_t n_blocks);
+size_t rf_tfenc_lds_bytes(int32_t L, int32_t d_model, int32_t heads, int32_t ffn_hidden);
+int rf_tfenc_pack(int32_t block, int32_t d_model, int32_t ffn_hidden, int32_t n_blocks, const float* Wq, const float* bq,
+                  const float* Wk, const float* bk, const float* Wv, const float* bv, const float* gamma1,
+                  const float* beta1, const float* W1, const float* b1, const float* W2, const float* b2,
+                  const float* gamma2, const float* beta2, void* packed, void* stream);
+int rf_tfenc_fwd(const void* x, int32_t x_dtype, int64_t x_stride_b, int64_t x_stride_l, const float* mask, int32_t batch,
+                 int32_t L, int32_t d_model, int32_t heads, int32_t ffn_hidden, int32_t n_blocks, const void* packed,
+                 float eps, float* out, int64_t out_stride_b, int64_t out_stride_l, void* stream);
+
 /*
  * Measurement probes (not a reference operator: the ceilings SURVEY §8d states the hot path against).
  * rf_stream_copy: dst = src, n_bytes % 16 == 0, 16-byte aligned; float4 STREAM copy (2 * n_bytes of HBM traffic);

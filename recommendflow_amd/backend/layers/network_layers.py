@@ -1,8 +1,10 @@
-"""Feature-interaction layers (reference: backend/layers/network_layers.py) on rf_interact.hip:
+"""Feature-interaction layers (reference: backend/layers/network_layers.py) on rf_interact.hip and rf_tfenc.hip:
 
-  FM_Layer, New_FM  -> rf_fm_fwd     (:43-56, :193-207)
-  CrossNetwork      -> rf_cross_fwd  (:163-171)
-  CIN               -> rf_cin_fwd    (:238-255)
+  FM_Layer, New_FM    -> rf_fm_fwd     (:43-56, :193-207)
+  CrossNetwork        -> rf_cross_fwd  (:163-171)
+  CIN                 -> rf_cin_fwd    (:238-255)
+  FFN                 -> two Dense     (:301-316)
+  TransformerEncoder  -> rf_tfenc_fwd  (:319-352), transformer_encoder_stack: several blocks in one launch
 
 Weights are created on the first call from the input shape, as Keras `build` does: 'random_normal' and
 tf.random_normal_initializer() are N(0, 0.05^2), w0 starts at zero. FM_Layer, New_FM, CrossNetwork and CIN are the
@@ -23,6 +25,8 @@ from typing import Dict, Optional, Sequence
 import torch
 
 from ...runtime import lib as L
+from .attention_layers import MultiHeadAttention
+from .core import Dense, LayerNormalization, Norm
 from .layer_utils import index_mapping
 
 
@@ -237,6 +241,133 @@ class CIN(torch.nn.Module):
         L.call("rf_cin_fwd", L.ptr(x), L.torch_dtype_code(x.dtype), x.stride(0), x.stride(1), B, fields, dim, self._sizes, K,
                L.ptr(self._packed), L.ptr(out), out.stride(0), L.ptr(ws), ws.numel(), L.stream_ptr())
         return out
+
+
+class FFN(torch.nn.Module):
+    """The position-wise feed-forward network (network_layers.py:301-316): Conv1D with kernel size 1 is a Dense over
+    the last axis. conv1: d_model -> hidden_unit with relu, conv2: hidden_unit -> d_model, both with bias, fp32
+    (glorot_uniform kernels, zero biases). On its own it is two Dense launches; inside TransformerEncoder the fused
+    kernel reads its weights."""
+
+    def __init__(self, hidden_unit, d_model, seed: int = 0, device="cuda"):
+        super().__init__()
+        self.hidden_unit, self.d_model = int(hidden_unit), int(d_model)
+        self.conv1 = Dense(self.d_model, self.hidden_unit, activation="relu", dtype=torch.float32, seed=seed + 1, device=device)
+        self.conv2 = Dense(self.hidden_unit, self.d_model, activation=None, dtype=torch.float32, seed=seed + 2, device=device)
+
+    def forward(self, inputs: torch.Tensor) -> torch.Tensor:
+        shape = inputs.shape
+        x = inputs.reshape(-1, shape[-1])
+        return self.conv2(self.conv1(x)).reshape(*shape[:-1], self.d_model)
+
+
+class TransformerEncoder(torch.nn.Module):
+    """One encoder block (network_layers.py:319-352): out1 = LN1(x + MHA(x, x, x, mask)), out = LN2(out1 + FFN(out1)),
+    both dropouts the identity (inference), in one rf_tfenc_fwd launch. forward([x, mask]): x [B, L, d_model] f32 or
+    bf16, read in place (any batch / row stride, e.g. the fused encoder's [B, S * 2D] output viewed as [B, S, 2D]);
+    mask [B, L], [B, L, 1] or None, zero marking a QUERY row (its attention is the mean of v over all keys, as the
+    reference's broadcast gives). Returns F32 [B, L, d_model], or fills `out` (a view with unit stride on d_model).
+
+    mha (wq / wk / wv in fp32), ffn (conv1 / conv2), layernorm1 and layernorm2 hold the fp32 master parameters; the
+    kernel reads a packed image of them, built on the device on the first call and again after load_state_dict or
+    refresh() (assign to a parameter in place, then call refresh()). The state dict holds the parameters in the
+    layers' own layouts (Dense keeps its kernel as [out][in])."""
+
+    _STATE = (("wq_kernel", "mha.wq.weight"), ("wq_bias", "mha.wq.bias"), ("wk_kernel", "mha.wk.weight"),
+              ("wk_bias", "mha.wk.bias"), ("wv_kernel", "mha.wv.weight"), ("wv_bias", "mha.wv.bias"),
+              ("conv1_kernel", "ffn.conv1.weight"), ("conv1_bias", "ffn.conv1.bias"),
+              ("conv2_kernel", "ffn.conv2.weight"), ("conv2_bias", "ffn.conv2.bias"),
+              ("ln1_gamma", "layernorm1.gamma"), ("ln1_beta", "layernorm1.beta"),
+              ("ln2_gamma", "layernorm2.gamma"), ("ln2_beta", "layernorm2.beta"))
+
+    def __init__(self, d_model, num_heads=1, ffn_hidden_unit=128, dropout=0., layer_norm_eps=1e-6, seed: int = 0,
+                 device="cuda"):
+        super().__init__()
+        L.load()
+        L.require_gpu()
+        self.d_model, self.num_heads, self.ffn_hidden_unit = int(d_model), int(num_heads), int(ffn_hidden_unit)
+        self.dropout, self.layer_norm_eps = dropout, float(layer_norm_eps)
+        self.seed, self.device = seed, device
+        self.mha = MultiHeadAttention(self.d_model, self.num_heads, seed=seed, device=device, proj_dtype=torch.float32)
+        self.ffn = FFN(self.ffn_hidden_unit, self.d_model, seed=seed + 3, device=device)
+        self.layernorm1 = Norm(LayerNormalization(epsilon=self.layer_norm_eps), self.d_model, device=device)
+        self.layernorm2 = Norm(LayerNormalization(epsilon=self.layer_norm_eps), self.d_model, device=device)
+        # the sub-layers keep plain tensors; the same tensors are this module's buffers, so that state_dict /
+        # load_state_dict (an in-place copy) see them
+        for name, path in self._STATE:
+            obj = self
+            for part in path.split("."):
+                obj = getattr(obj, part)
+            self.register_buffer(name, obj)
+        self._gen = 0          # bumped whenever the masters may have changed
+        self._stack = None     # (key, image) of the last stack this block led
+
+    def shape_key(self):
+        return (self.d_model, self.num_heads, self.ffn_hidden_unit, self.layer_norm_eps)
+
+    def refresh(self):
+        """Drop the packed image: the next call packs it again from the fp32 masters."""
+        self._gen += 1
+        self._stack = None
+
+    def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
+        super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
+        self.refresh()
+
+    def _pack_into(self, packed: torch.Tensor, block: int, n_blocks: int):
+        f = lambda name: L.ptr(getattr(self, name))  # noqa: E731
+        # Dense keeps [out][in]; the ABI takes the Keras (in, out) kernels
+        kern = {n: getattr(self, n).t().contiguous() for n in ("wq_kernel", "wk_kernel", "wv_kernel", "conv1_kernel", "conv2_kernel")}
+        L.call("rf_tfenc_pack", block, self.d_model, self.ffn_hidden_unit, n_blocks, L.ptr(kern["wq_kernel"]), f("wq_bias"),
+               L.ptr(kern["wk_kernel"]), f("wk_bias"), L.ptr(kern["wv_kernel"]), f("wv_bias"), f("ln1_gamma"), f("ln1_beta"),
+               L.ptr(kern["conv1_kernel"]), f("conv1_bias"), L.ptr(kern["conv2_kernel"]), f("conv2_bias"), f("ln2_gamma"),
+               f("ln2_beta"), L.ptr(packed), L.stream_ptr())
+
+    def forward(self, inputs, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        x, mask = inputs
+        return transformer_encoder_stack([self], x, mask, out=out)
+
+
+def transformer_encoder_stack(blocks: Sequence[TransformerEncoder], x: torch.Tensor, mask: Optional[torch.Tensor] = None,
+                              out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """blocks[-1](... blocks[0]([x, mask]) ..., mask) in ONE rf_tfenc_fwd launch through one packed image of all blocks
+    (cached on blocks[0] until one of them is refreshed or reloaded). The blocks must have equal shapes (d_model,
+    num_heads, ffn_hidden_unit, layer_norm_eps): ValueError otherwise."""
+    L.require_gpu()
+    blocks = list(blocks)
+    if not blocks:
+        raise ValueError("transformer_encoder_stack needs at least one block")
+    lead = blocks[0]
+    for blk in blocks[1:]:
+        if blk.shape_key() != lead.shape_key():
+            raise ValueError(f"blocks of one stack must have equal shapes: {blk.shape_key()} != {lead.shape_key()}")
+    x = _dense_view(x)
+    B, Ln, d = x.shape
+    if d != lead.d_model:
+        raise ValueError(f"TransformerEncoder was built for d_model {lead.d_model}, got {d}")
+    n = len(blocks)
+    lib = L.load()
+    key = tuple((id(blk), blk._gen) for blk in blocks)
+    if lead._stack is None or lead._stack[0] != key:
+        nbytes = int(lib.rf_tfenc_packed_bytes(lead.d_model, lead.ffn_hidden_unit, n))
+        if nbytes == 0:
+            L.check(L.RF_EINVAL, "rf_tfenc_packed_bytes")
+        packed = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+        for i, blk in enumerate(blocks):
+            blk._pack_into(packed, i, n)
+        lead._stack = (key, packed)
+    packed = lead._stack[1]
+    m = None
+    if mask is not None:
+        m = mask.reshape(B, Ln).to(device=x.device, dtype=torch.float32).contiguous()
+    if out is None:
+        out = torch.empty((B, Ln, d), dtype=torch.float32, device=x.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (B, Ln, d) or (d > 1 and out.stride(2) != 1):
+        raise ValueError(f"out must be an F32 [{B}, {Ln}, {d}] view with unit stride on the last axis")
+    L.call("rf_tfenc_fwd", L.ptr(x), L.torch_dtype_code(x.dtype), x.stride(0), x.stride(1), L.ptr(m), B, Ln, d, lead.num_heads,
+           lead.ffn_hidden_unit, n, L.ptr(packed), lead.layer_norm_eps, L.ptr(out), out.stride(0), out.stride(1),
+           L.stream_ptr())
+    return out
 
 
 # ---- training ----------------------------------------------------------------------------------------------------------
