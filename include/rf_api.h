@@ -1054,6 +1054,44 @@ int rf_tfenc_fwd(const void* x, int32_t x_dtype, int64_t x_stride_b, int64_t x_s
                  int32_t L, int32_t d_model, int32_t heads, int32_t ffn_hidden, int32_t n_blocks, const void* packed,
                  float eps, float* out, int64_t out_stride_b, int64_t out_stride_l, void* stream);
 
+/* ---- TransformerEncoder, backward (rf_tfenc_bwd.hip) -------------------------------------------------------- */
+/*
+ * The gradient of rf_tfenc_fwd's stack with respect to x and the 14 parameters of every block, given dout (F32, element
+ * strides dout_stride_b / dout_stride_l, read in place). Recompute: the forward saves nothing; rf_tfenc_bwd reads x,
+ * mask, the forward's image `packed` (for the fp32 vectors) and `packed_t`, the bf16 row-major copies of Wq | Wk | Wv, W1
+ * and W2 in both orientations that rf_tfenc_bwd_pack builds per block from the fp32 masters in Keras layouts
+ * (rf_tfenc_bwd_packed_bytes bytes, 16-byte aligned, all blocks). Per block from the last to the first, with r1 = x + att
+ * and r2 = out1 + ffn: LayerNorm 2 backward (biased variance, the forward's eps); db2 = sum dr2, dW2 = h^T dr2,
+ * dh = (dr2 W2^T) [pre > 0] (0 at pre = 0), db1 = sum dh, dW1 = out1^T dh, d_out1 = dr2 + dh W1^T; LayerNorm 1 backward,
+ * datt = dr1; per head dP = datt v^T, dv = P^T datt, dS = P (dP - rowsum(dP P)), dq = dS k / sqrt(depth),
+ * dk = dS^T q / sqrt(depth); dW{q,k,v} = x^T d{q,k,v}, db{q,k,v} the row sums, dx = dr1 + dq Wq^T + dk Wk^T + dv Wv^T.
+ * A masked query row has P = 1 / L and dS = 0 exactly (nothing reaches dq, dk, dWq, dWk, dbq through it; its P carries datt
+ * into dv); keys padded in beyond L add exactly zero everywhere; dbk is mathematically zero and comes out as rounding
+ * noise.
+ * dx: F32, element strides dx_stride_b / dx_stride_l as rf_tfenc_fwd's out; only [batch][L][d_model] of the view is
+ * written; it may not overlap dout. grads: a HOST array of 14 n_blocks device pointers, per block in rf_tfenc_pack's order
+ * (Wq bq Wk bk Wv bv gamma1 beta1 W1 b1 W2 b2 gamma2 beta2), F32 in Keras layouts, overwritten. ws: rf_tfenc_bwd_ws_bytes
+ * bytes, 16-byte aligned: the fp32 input of every block, one set of [batch L][d_model] / [batch L][ffn_hidden] tensors
+ * (fp32 or bf16) reused by the blocks, bf16 copies [batch][d_model][L padded to 32] of q k v and datt, three scalars per
+ * [batch][heads][L] and the chunk partials of the parameter gradients; nothing of size [batch][heads][L][L] exists.
+ * Precision: every MFMA operand is an fp32 value rounded once (RNE) to bf16: the recomputed forward operands at the
+ * forward's rounding points, and dr2, dh, datt, dS / sqrt(depth), dq, dk, dv and the weights; accumulation is fp32. Both
+ * LayerNorm backwards, the softmax backward on the unrounded P, the residual gradient stream, dx and every parameter
+ * gradient are fp32 (db1, dbq, dbk, dbv sum the rounded dh, dq, dk, dv). Deterministic: no atomics; the contraction over
+ * the batch L rows runs in chunks whose length depends on batch L only, added in chunk order.
+ * Limits: rf_tfenc_fwd's, LDS limit included (a refused shape names "LDS"); the backward keeps nothing resident beyond a
+ * 10 KiB staging tile. rf_tfenc_bwd_ws_bytes and rf_tfenc_bwd_packed_bytes return 0 with the error set for a refused
+ * shape. batch 0 validates and returns RF_OK without a launch (the caller zeroes the gradients).
+ */
+size_t rf_tfenc_bwd_packed_bytes(int32_t d_model, int32_t ffn_hidden, int32_t n_blocks);
+int rf_tfenc_bwd_pack(int32_t block, int32_t d_model, int32_t ffn_hidden, int32_t n_blocks, const float* Wq, const float* Wk,
+                      const float* Wv, const float* W1, const float* W2, void* packed_t, void* stream);
+size_t rf_tfenc_bwd_ws_bytes(int32_t batch, int32_t L, int32_t d_model, int32_t heads, int32_t ffn_hidden, int32_t n_blocks);
+int rf_tfenc_bwd(const void* x, int32_t x_dtype, int64_t x_stride_b, int64_t x_stride_l, const float* mask, int32_t batch,
+                 int32_t L, int32_t d_model, int32_t heads, int32_t ffn_hidden, int32_t n_blocks, const void* packed,
+                 const void* packed_t, float eps, const float* dout, int64_t dout_stride_b, int64_t dout_stride_l, float* dx,
+                 int64_t dx_stride_b, int64_t dx_stride_l, float* const* grads, void* ws, size_t ws_bytes, void* stream);
+
 /*
  * Measurement probes (not a reference operator: the ceilings SURVEY §8d states the hot path against).
  * rf_stream_copy: dst = src, n_bytes % 16 == 0, 16-byte aligned; float4 STREAM copy (2 * n_bytes of HBM traffic);

@@ -681,3 +681,162 @@ class TrainCIN(CIN):
 
     def regularization(self) -> torch.Tensor:
         return sum(_l2(self.l2_reg, p) for p in self.cin_W.values())
+
+
+# the order of rf_tfenc_pack's parameters and of rf_tfenc_bwd's grads, per block
+_TFENC_ABI = ("wq_kernel", "wq_bias", "wk_kernel", "wk_bias", "wv_kernel", "wv_bias", "ln1_gamma", "ln1_beta",
+              "conv1_kernel", "conv1_bias", "conv2_kernel", "conv2_bias", "ln2_gamma", "ln2_beta")
+
+
+def _tfenc_pack_transposed(blocks) -> torch.Tensor:
+    """rf_tfenc_bwd_pack: the bf16 copies of every block's five kernels that rf_tfenc_bwd reads, from the masters."""
+    lead, n = blocks[0], len(blocks)
+    nbytes = int(L.load().rf_tfenc_bwd_packed_bytes(lead.d_model, lead.ffn_hidden_unit, n))
+    if nbytes == 0:
+        L.check(L.RF_EINVAL, "rf_tfenc_bwd_packed_bytes")
+    packed = torch.empty(nbytes, dtype=torch.uint8, device=lead.wq_kernel.device)
+    with torch.no_grad():
+        for i, blk in enumerate(blocks):
+            # Dense keeps [out][in]; the ABI takes the Keras (in, out) kernels
+            kern = [getattr(blk, nm).detach().t().contiguous()
+                    for nm in ("wq_kernel", "wk_kernel", "wv_kernel", "conv1_kernel", "conv2_kernel")]
+            L.call("rf_tfenc_bwd_pack", i, lead.d_model, lead.ffn_hidden_unit, n, *[L.ptr(k) for k in kern], L.ptr(packed),
+                   L.stream_ptr())
+    return packed
+
+
+class _TfencFn(torch.autograd.Function):
+    """out = rf_tfenc_fwd(x) over the whole stack (into `out` if given: a view of the caller's buffer, marked dirty, so
+    that the gradient of whatever reads the buffer comes back here; autograd's in-place bookkeeping needs it to be the
+    first input); backward = rf_tfenc_bwd reading dout in place through its strides. Saves x and the mask only: the kernel recomputes.
+    params are the blocks' 14 master parameters each, in _TFENC_ABI order (autograd hands their gradients back in the
+    masters' own layouts); the kernels read the packed images."""
+
+    @staticmethod
+    def forward(ctx, out, x, blocks, mask, packed, *params):
+        B, Ln, d = x.shape
+        lead, n = blocks[0], len(blocks)
+        if out is None:
+            out = torch.empty((B, Ln, d), dtype=torch.float32, device=x.device)
+        else:
+            ctx.mark_dirty(out)
+        L.call("rf_tfenc_fwd", L.ptr(x), L.torch_dtype_code(x.dtype), x.stride(0), x.stride(1), L.ptr(mask), B, Ln, d,
+               lead.num_heads, lead.ffn_hidden_unit, n, L.ptr(packed), lead.layer_norm_eps, L.ptr(out), out.stride(0),
+               out.stride(1), L.stream_ptr())
+        ctx.save_for_backward(x, mask)
+        ctx.blocks, ctx.packed = blocks, packed
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        x, mask = ctx.saved_tensors
+        blocks = ctx.blocks
+        lead, n = blocks[0], len(blocks)
+        B, Ln, d = x.shape
+        ffn = lead.ffn_hidden_unit
+        dout = dout.float()
+        if (d > 1 and dout.stride(2) != 1) or dout.stride(1) < d or dout.stride(0) < 0:  # e.g. an expanded scalar
+            dout = dout.contiguous()
+        dev = x.device
+        if B == 0:  # an empty tensor keeps whatever strides it has
+            dout = torch.empty((0, Ln, d), dtype=torch.float32, device=dev)
+        dx = torch.empty((B, Ln, d), dtype=torch.float32, device=dev)
+        keras = {"wq_kernel": (d, d), "wk_kernel": (d, d), "wv_kernel": (d, d), "conv1_kernel": (d, ffn),
+                 "conv2_kernel": (ffn, d), "conv1_bias": (ffn,)}
+        alloc = torch.zeros if B == 0 else torch.empty
+        grads = [alloc(keras.get(nm, (d,)), dtype=torch.float32, device=dev) for _ in blocks for nm in _TFENC_ABI]
+        wsb = int(L.load().rf_tfenc_bwd_ws_bytes(B, Ln, d, lead.num_heads, ffn, n))
+        if wsb == 0:
+            L.check(L.RF_EINVAL, "rf_tfenc_bwd_ws_bytes")
+        ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+        packed_t = _tfenc_pack_transposed(blocks)
+        ptrs = (ctypes.c_void_p * len(grads))(*[g.data_ptr() for g in grads])
+        L.call("rf_tfenc_bwd", L.ptr(x), L.torch_dtype_code(x.dtype), x.stride(0), x.stride(1), L.ptr(mask), B, Ln, d,
+               lead.num_heads, ffn, n, L.ptr(ctx.packed), L.ptr(packed_t), lead.layer_norm_eps, L.ptr(dout), dout.stride(0),
+               dout.stride(1), L.ptr(dx), dx.stride(0), dx.stride(1), ptrs, L.ptr(ws), ws.numel(), L.stream_ptr())
+        if dx.dtype != x.dtype:
+            dx = dx.to(x.dtype)
+        # the masters' layouts: Dense keeps its kernel as [out][in]
+        grads = [g.t().contiguous() if g.dim() == 2 else g for g in grads]
+        return (None, dx if ctx.needs_input_grad[1] else None, None, None, None, *grads)
+
+
+class TrainTransformerEncoder(TransformerEncoder):
+    """TransformerEncoder under training: the fourteen tensors are Parameters under the names of TransformerEncoder's
+    buffers (the two classes load each other's state dicts; mha, ffn, layernorm1 and layernorm2 still see the same
+    storage), gradients reach them and the input through rf_tfenc_bwd (everything is recomputed; the forward saves x and
+    the mask only). regularization() is l2_reg * the sum of the five kernels squared.
+
+    The optimizer writes the masters through raw pointers, which no torch version counter sees, so in training mode the
+    forward image is packed from them on every forward and the transposed image in the backward; eval packs lazily as
+    TransformerEncoder does. train() / eval() and load_state_dict drop the cached image. The kernel has no dropout:
+    dropout > 0 in training mode raises ValueError (deviation D-tfenc-dropout; the reference's default is 0)."""
+
+    def __init__(self, d_model, num_heads=1, ffn_hidden_unit=128, dropout=0., layer_norm_eps=1e-6, l2_reg: float = 0.,
+                 seed: int = 0, device="cuda"):
+        super().__init__(d_model, num_heads=num_heads, ffn_hidden_unit=ffn_hidden_unit, dropout=dropout,
+                         layer_norm_eps=layer_norm_eps, seed=seed, device=device)
+        self.l2_reg = float(l2_reg)
+        for name, _ in self._STATE:
+            t = self._buffers.pop(name)
+            self.register_parameter(name, torch.nn.Parameter(t))  # the sub-layer's tensor: the same storage
+
+    def train(self, mode: bool = True):
+        self.refresh()
+        return super().train(mode)
+
+    def forward(self, inputs, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        x, mask = inputs
+        return train_transformer_encoder_stack([self], x, mask, out=out)
+
+    def regularization(self) -> torch.Tensor:
+        return sum(_l2(self.l2_reg, getattr(self, n)) for n in ("wq_kernel", "wk_kernel", "wv_kernel", "conv1_kernel",
+                                                                "conv2_kernel"))
+
+
+def train_transformer_encoder_stack(blocks: Sequence[TrainTransformerEncoder], x: torch.Tensor,
+                                    mask: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """transformer_encoder_stack under training: ONE autograd node over the whole stack, rf_tfenc_fwd forward (into `out`
+    if given, e.g. the left columns of a concat buffer viewed as [B, L, d_model]) and rf_tfenc_bwd backward. dx comes
+    back in x's dtype, rounded once. With every block in eval mode, or without grad, it is transformer_encoder_stack."""
+    blocks = list(blocks)
+    if not blocks:
+        raise ValueError("train_transformer_encoder_stack needs at least one block")
+    training = any(blk.training for blk in blocks)
+    if training:
+        for blk in blocks:
+            if blk.dropout > 0:
+                raise ValueError(f"TrainTransformerEncoder: dropout ({blk.dropout}) > 0 cannot be trained: rf_tfenc_fwd has "
+                                 "no dropout")
+    if not training or not torch.is_grad_enabled():
+        with torch.no_grad():
+            if training:
+                for blk in blocks:
+                    blk.refresh()
+            return transformer_encoder_stack(blocks, x, mask, out=out)
+    L.require_gpu()
+    lead = blocks[0]
+    for blk in blocks[1:]:
+        if blk.shape_key() != lead.shape_key():
+            raise ValueError(f"blocks of one stack must have equal shapes: {blk.shape_key()} != {lead.shape_key()}")
+    x = _dense_view(x)
+    B, Ln, d = x.shape
+    if d != lead.d_model:
+        raise ValueError(f"TransformerEncoder was built for d_model {lead.d_model}, got {d}")
+    n = len(blocks)
+    nbytes = int(L.load().rf_tfenc_packed_bytes(lead.d_model, lead.ffn_hidden_unit, n))
+    if nbytes == 0:
+        L.check(L.RF_EINVAL, "rf_tfenc_packed_bytes")
+    if int(L.load().rf_tfenc_bwd_ws_bytes(B, Ln, d, lead.num_heads, lead.ffn_hidden_unit, n)) == 0:
+        L.check(L.RF_EINVAL, "rf_tfenc_bwd_ws_bytes")  # fail before the forward
+    packed = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+    with torch.no_grad():
+        for i, blk in enumerate(blocks):
+            blk._pack_into(packed, i, n)
+    m = None
+    if mask is not None:
+        m = mask.reshape(B, Ln).to(device=x.device, dtype=torch.float32).contiguous()
+    if out is not None and (out.dtype != torch.float32 or tuple(out.shape) != (B, Ln, d) or (d > 1 and out.stride(2) != 1)):
+        raise ValueError(f"out must be an F32 [{B}, {Ln}, {d}] view with unit stride on the last axis")
+    params = [getattr(blk, nm) for blk in blocks for nm in _TFENC_ABI]
+    return _TfencFn.apply(out, x, blocks, m, packed, *params)

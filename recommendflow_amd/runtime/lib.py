@@ -171,6 +171,11 @@ _SIGS = {
     "rf_tfenc_pack": (ctypes.c_int, [_i32, _i32, _i32, _i32] + [_vp] * 14 + [_vp, _vp]),
     "rf_tfenc_fwd": (ctypes.c_int, [_vp, _i32, _i64, _i64, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _f32, _vp, _i64, _i64,
                                     _vp]),
+    "rf_tfenc_bwd_packed_bytes": (ctypes.c_size_t, [_i32, _i32, _i32]),
+    "rf_tfenc_bwd_pack": (ctypes.c_int, [_i32, _i32, _i32, _i32] + [_vp] * 5 + [_vp, _vp]),
+    "rf_tfenc_bwd_ws_bytes": (ctypes.c_size_t, [_i32, _i32, _i32, _i32, _i32, _i32]),
+    "rf_tfenc_bwd": (ctypes.c_int, [_vp, _i32, _i64, _i64, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _f32, _vp, _i64,
+                                    _i64, _vp, _i64, _i64, _vp, _vp, ctypes.c_size_t, _vp]),
 }
 EXPORTED = tuple(_SIGS)
 # include/rf_diag.h: tools-only entry points (not the production ABI)
