@@ -431,7 +431,10 @@ int rf_esim_gather_stats_fwd(const uint32_t* q_ids, const uint32_t* a_ids, const
  *   the reference's [..., Lq, 1] mask broadcasts over keys); softmax over keys (fp32); out = P v.
  * q: [batch][Lq][heads*depth], k, v: [batch][Lk][heads*depth] (dtype F16 or BF16, contiguous; head h
  * owns columns [h*depth, (h+1)*depth)); mask: F32 [batch][Lq] (NULL = no mask).
- * out: F32 [batch][Lq][heads*depth]. Constraints: 1 <= Lq, Lk <= 256, depth in {32, 64, 128}.
+ * out: F32 [batch][Lq][heads*depth]. q, k, v 16-byte aligned; batch >= 0 (0 validates and launches nothing).
+ * Constraints: 1 <= Lq <= 4096, 1 <= Lk <= 256, depth in {32, 64, 128}, and the workgroup's LDS,
+ * 2*Lkp*(depth+8)*2 + 4*16*(Lkp+8)*2 bytes with Lkp = Lk rounded up to 32, at most 160 KiB: at depth 128 that
+ * leaves Lk <= 224 (depth 32 and 64 take every Lk <= 256). Anything else is RF_EINVAL, whatever the batch.
  */
 int rf_sdpa_fwd(const void* q, const void* k, const void* v, int32_t dtype, int32_t batch, int32_t heads,
                 int32_t Lq, int32_t Lk, int32_t depth, const float* mask, float* out, void* stream);

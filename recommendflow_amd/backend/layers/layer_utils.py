@@ -16,7 +16,12 @@ def scaled_dot_product_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tens
     (split_heads, :27-38). mask: [B, Lq] or [B, Lq, 1] — zero marks a QUERY row whose logits are all
     replaced (the reference's [..., Lq, 1] mask broadcasts over keys). Returns fp32 [B, Lq, heads*depth]
     (the merged-heads layout of MultiHeadAttention.call, attention_layers.py:167). Logits and softmax
-    are fp32 inside the kernel; operands are rounded to `dtype` (fp16 for cfg5) for the MFMA.
+    are fp32 inside the kernel; operands are rounded to `dtype` (fp16 for cfg5) for the MFMA, and the
+    probabilities are rounded to `dtype` once before P @ v.
+
+    Limits (rf_sdpa_fwd; anything else raises ValueError before a launch): 1 <= Lq <= 4096, 1 <= Lk <= 256,
+    depth in {32, 64, 128}, dtype fp16 or bf16, and at most 160 KiB of LDS per workgroup, which at depth 128
+    leaves Lk <= 224.
     """
     L.require_gpu()
     B, Lq, width = q.shape

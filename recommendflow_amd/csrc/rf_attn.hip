@@ -1365,13 +1365,19 @@ extern "C" int rf_sdpa_fwd(const void* q, const void* k, const void* v, int32_t 
                            int32_t Lq, int32_t Lk, int32_t depth, const float* mask, float* out, void* stream) {
     RF_REQUIRE(dtype == RF_DTYPE_BF16 || dtype == RF_DTYPE_F16, "rf_sdpa_fwd: dtype must be BF16 or F16");
     RF_REQUIRE(depth == 32 || depth == 64 || depth == 128, "rf_sdpa_fwd: depth must be 32, 64 or 128 (got %d)", depth);
-    RF_REQUIRE(Lq >= 1 && Lq <= 4096 && Lk >= 1 && Lk <= 256, "rf_sdpa_fwd: need 1 <= Lk <= 256 and Lq >= 1");
-    RF_REQUIRE(batch >= 0 && heads >= 1, "rf_sdpa_fwd: batch >= 0, heads >= 1");
+    RF_REQUIRE(Lk >= 1 && Lk <= 256, "rf_sdpa_fwd: need 1 <= Lk <= 256 (got %d)", Lk);
+    RF_REQUIRE(Lq >= 1 && Lq <= 4096, "rf_sdpa_fwd: need 1 <= Lq <= 4096 (got %d)", Lq);
+    RF_REQUIRE(batch >= 0, "rf_sdpa_fwd: need batch >= 0 (got %d)", batch);
+    RF_REQUIRE(heads >= 1, "rf_sdpa_fwd: need heads >= 1 (got %d)", heads);
     RF_REQUIRE(((uintptr_t)q & 15) == 0 && ((uintptr_t)k & 15) == 0 && ((uintptr_t)v & 15) == 0, "rf_sdpa_fwd: q/k/v must be 16-byte aligned");
-    if (batch == 0) return RF_OK;
-    RF_REQUIRE(q && k && v && out, "rf_sdpa_fwd: null pointer");
+    // k and v images of Lkp rows (row stride depth + 8) and one 16 x (Lkp + 8) P tile per wave: a property of the shape
+    // alone, so it is refused here whatever the batch (at depth 128 this leaves Lk <= 224)
     const int Lkp = (Lk + 31) & ~31;
     const size_t lds = (size_t)2 * Lkp * (depth + 8) * 2 + (size_t)4 * 16 * (Lkp + 8) * 2;
+    RF_REQUIRE(lds <= 160 * 1024, "rf_sdpa_fwd: Lk %d at depth %d needs %zu bytes of LDS (> 160 KiB); depth 128 takes Lk <= 224",
+               Lk, depth, lds);
+    if (batch == 0) return RF_OK;
+    RF_REQUIRE(q && k && v && out, "rf_sdpa_fwd: null pointer");
     hipStream_t st = rf_stream(stream);
     const int grid = batch * heads;
 #define RF_SDPA_LAUNCH(F16, DEP)                                                                                    \
