@@ -110,7 +110,6 @@ class TrainLNMLP:
             raise RuntimeError("TrainLNMLP.backward before forward")
         cache, rate, seeds = self._cache
         st = L.stream_ptr(stream)
-        lib = L.load()
         if dh.stride(-1) != 1:
             dh = dh.contiguous()
         dx = None
@@ -123,7 +122,7 @@ class TrainLNMLP:
             dpbuf = (torch.zeros if padded else torch.empty)((Mp, Np), dtype=torch.float32, device=pre.device)
             dpre = dpbuf[:M, :N]
             db = torch.empty(N, dtype=torch.float32, device=pre.device)
-            ws = torch.empty(max(int(lib.rf_tower_ws_bytes(M, N)), 4), dtype=torch.uint8, device=pre.device)
+            ws = L.workspace("rf_tower_ws_bytes", pre.device, M, N)
             L.call("rf_act_dropout_bwd", L.ptr(dh), dh.stride(0), L.ptr(pre), pre.stride(0), M, N, self.act, rate, seeds[l],
                    L.ptr(dpre), dpre.stride(0), L.ptr(db), L.ptr(ws), ws.numel(), st)
             dW = GM.gemm_f32(dpbuf, zbuf, trans_a=True, stream=st)
@@ -133,7 +132,7 @@ class TrainLNMLP:
             dxl = torch.empty((M, K), dtype=torch.float32, device=pre.device)
             dg = torch.empty(K, dtype=torch.float32, device=pre.device)
             dbt = torch.empty(K, dtype=torch.float32, device=pre.device)
-            wsl = torch.empty(max(int(lib.rf_layernorm_bwd_ws_bytes(M, K)), 4), dtype=torch.uint8, device=pre.device)
+            wsl = L.workspace("rf_layernorm_bwd_ws_bytes", pre.device, M, K)
             L.call("rf_layernorm_bwd", L.ptr(dz), dz.stride(0), L.ptr(x), x.stride(0), M, K, L.ptr(self.gamma[l]), self.eps,
                    L.ptr(dxl), dxl.stride(0), L.ptr(dg), L.ptr(dbt), L.ptr(wsl), wsl.numel(), st)
             self.gamma[l].grad, self.beta[l].grad = dg, dbt

@@ -31,10 +31,6 @@ def layer_seed(base: int, step: int, layer: int) -> int:
     return x
 
 
-def _ws(M: int, K: int, device) -> torch.Tensor:
-    return torch.empty(max(int(L.load().rf_tower_ws_bytes(M, K)), 4), dtype=torch.uint8, device=device)
-
-
 def _gemm_layer(probs, trans_a: bool, trans_b: bool, stream):
     """One layer's GEMMs of every tower (forward, weight gradient or input gradient): probs = [(a, b, bias, act name,
     out)]. librf (rf_gemm_f32: stream-K exact-fp32 MFMA, grouped into one launch where runtime.gemm.group_pays) when
@@ -81,7 +77,7 @@ def _towers_forward(towers, xs, params_list):
             M = h.shape[0]
             mean = torch.empty(K, dtype=torch.float32, device=dev)
             var = torch.empty(K, dtype=torch.float32, device=dev)
-            ws = _ws(M, K, dev)
+            ws = L.workspace("rf_tower_ws_bytes", dev, M, K)
             L.call("rf_col_stats", L.ptr(h), M, K, h.stride(0), L.ptr(mean), L.ptr(var), L.ptr(ws), ws.numel(), st)
             Wf = torch.empty_like(W)
             bf = torch.empty(N, dtype=torch.float32, device=dev)
@@ -142,7 +138,7 @@ def _towers_backward(runs: Sequence[_TowerViews]):
             N, K = r.params[4 * l].shape
             h_in = r.x if l == 0 else r.outs[l - 1]
             M = h_in.shape[0]
-            ws = _ws(M, max(K, N), dev)
+            ws = L.workspace("rf_tower_ws_bytes", dev, M, max(K, N))
             dpre = torch.empty((M, N), dtype=torch.float32, device=dev)
             db = torch.empty(N, dtype=torch.float32, device=dev)
             L.call("rf_selu_dropout_bwd", L.ptr(dh), dh.stride(0), L.ptr(r.outs[l]), N, M, N, r.tower.rate,

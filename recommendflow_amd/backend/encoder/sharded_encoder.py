@@ -37,6 +37,7 @@ import torch
 
 from ...runtime import lib as L
 from ...runtime.batch import SparseBatch, from_lists
+from ...runtime.segment import segment_sum_rows
 from .sparse_encoder import POOLED, SLOT_DTYPE, SlotSpec
 
 
@@ -104,10 +105,9 @@ class GpuShardOps:
         perm = torch.empty(max(n, 1), dtype=torch.int32, device=self.device)
         inv = torch.empty(max(n, 1), dtype=torch.int32, device=self.device)
         local = torch.empty(max(n, 1), dtype=torch.int64, device=self.device)
-        ws_bytes = L.load().rf_bucketize_ws_bytes(n, nranks)
-        ws = torch.empty(max(int(ws_bytes), 1), dtype=torch.uint8, device=self.device)
+        ws = L.workspace("rf_bucketize_ws_bytes", self.device, n, nranks)
         L.call("rf_bucketize_owner", L.ptr(rows), n, nranks, L.ptr(counts), L.ptr(perm), L.ptr(inv), L.ptr(local), L.ptr(ws),
-               ws_bytes, L.stream_ptr(None))
+               ws.numel(), L.stream_ptr(None))
         return counts, perm[:n], local[:n], inv[:n]
 
     def route(self, rows: torch.Tensor, nranks: int, table_rows: int):
@@ -116,10 +116,9 @@ class GpuShardOps:
         counts = torch.empty(nranks, dtype=torch.int32, device=self.device)
         local = torch.empty(max(n, 1), dtype=torch.int64, device=self.device)
         row_map = torch.empty(max(n, 1), dtype=torch.int32, device=self.device)
-        ws_bytes = L.load().rf_route_ws_bytes(n, nranks, table_rows)
-        ws = torch.empty(max(int(ws_bytes), 1), dtype=torch.uint8, device=self.device)
+        ws = L.workspace("rf_route_ws_bytes", self.device, n, nranks, table_rows)
         L.call("rf_route_rows", L.ptr(rows), n, nranks, table_rows, L.ptr(counts), L.ptr(local), L.ptr(row_map), None,
-               L.ptr(ws), ws_bytes, L.stream_ptr(None))
+               L.ptr(ws), ws.numel(), L.stream_ptr(None))
         return counts, local, row_map[:n]
 
     def route_hash_build(self, rows: torch.Tensor, nranks: int, rank: int, table_rows: int):
@@ -128,11 +127,10 @@ class GpuShardOps:
         n = rows.numel()
         counts = torch.empty(nranks, dtype=torch.int32, device=self.device)
         row_map = torch.empty(max(n, 1), dtype=torch.int32, device=self.device)
-        ws_bytes = int(L.load().rf_route_hash_ws_bytes(n, nranks, table_rows))
-        ws = torch.empty(max(ws_bytes, 256), dtype=torch.uint8, device=self.device)
+        ws = L.workspace("rf_route_hash_ws_bytes", self.device, n, nranks, table_rows)
         L.call("rf_route_hash_build", L.ptr(rows), n, nranks, rank, table_rows, L.ptr(row_map), L.ptr(counts), L.ptr(ws),
-               ws_bytes, L.stream_ptr(None))
-        return counts, (n, nranks, table_rows, row_map, ws, ws_bytes)
+               ws.numel(), L.stream_ptr(None))
+        return counts, (n, nranks, table_rows, row_map, ws)
 
     def route_hash_build_tokens(self, desc, n_slots: int, batch: SparseBatch, tail: torch.Tensor, nranks: int,
                                 rank: int, table_rows: int):
@@ -141,20 +139,19 @@ class GpuShardOps:
         n = 2 * batch.n_tokens + tail.numel()
         counts = torch.empty(nranks, dtype=torch.int32, device=self.device)
         row_map = torch.empty(max(n, 1), dtype=torch.int32, device=self.device)
-        ws_bytes = int(L.load().rf_route_hash_ws_bytes(n, nranks, table_rows))
-        ws = torch.empty(max(ws_bytes, 256), dtype=torch.uint8, device=self.device)
+        ws = L.workspace("rf_route_hash_ws_bytes", self.device, n, nranks, table_rows)
         L.call("rf_route_hash_build_tokens", L.ptr(desc), n_slots, L.ptr(batch.tok_bytes), L.ptr(batch.tok_off),
                L.ptr(batch.bag_off), batch.batch, batch.n_tokens, L.ptr(tail), tail.numel(), nranks, rank, table_rows,
-               L.ptr(row_map), L.ptr(counts), L.ptr(ws), ws_bytes, L.stream_ptr(None))
-        return counts, (n, nranks, table_rows, row_map, ws, ws_bytes), n
+               L.ptr(row_map), L.ptr(counts), L.ptr(ws), ws.numel(), L.stream_ptr(None))
+        return counts, (n, nranks, table_rows, row_map, ws), n
 
     def route_hash_finish(self, state, n_uniq: int):
         """rf_route_hash_finish -> (local int64 [n_uniq], row_map int32 [n]). n_uniq = -1 (nranks <= 64): the
         distinct total is read on the device, so this can be enqueued before the host reads the counts; local then
         has n entries, of which the first sum(counts) are the distinct rows."""
-        n, nranks, table_rows, row_map, ws, ws_bytes = state
+        n, nranks, table_rows, row_map, ws = state
         local = torch.empty(max(n if n_uniq < 0 else n_uniq, 1), dtype=torch.int64, device=self.device)
-        L.call("rf_route_hash_finish", n, nranks, table_rows, n_uniq, L.ptr(local), L.ptr(row_map), L.ptr(ws), ws_bytes,
+        L.call("rf_route_hash_finish", n, nranks, table_rows, n_uniq, L.ptr(local), L.ptr(row_map), L.ptr(ws), ws.numel(),
                L.stream_ptr(None))
         return (local if n_uniq < 0 else local[:n_uniq]), row_map[:n]
 
@@ -172,10 +169,9 @@ class GpuShardOps:
         ent_unit = torch.empty(cap, dtype=torch.int32, device=dev)
         ent_mult = torch.empty(cap, dtype=torch.int32, device=dev)
         n_ent = torch.empty(1, dtype=torch.int32, device=dev)
-        wsb = int(L.load().rf_pp_ws_bytes(max(n_units, cap)))
-        ws = torch.empty(max(wsb, 256), dtype=torch.uint8, device=dev)
+        ws = L.workspace("rf_pp_ws_bytes", dev, max(n_units, cap))
         L.call("rf_pp_plan", L.ptr(desc), S, L.ptr(batch.bag_off), L.ptr(batch.lmax), B, batch.n_tokens, L.ptr(rows),
-               flags, L.ptr(ent_off), L.ptr(ent_row), L.ptr(ent_unit), L.ptr(ent_mult), L.ptr(n_ent), L.ptr(ws), wsb,
+               flags, L.ptr(ent_off), L.ptr(ent_row), L.ptr(ent_unit), L.ptr(ent_mult), L.ptr(n_ent), L.ptr(ws), ws.numel(),
                L.stream_ptr(None))
         n = int(n_ent.item())
         counts, perm, local, _ = self.bucketize(ent_row[:n], nranks)
@@ -184,7 +180,7 @@ class GpuShardOps:
         seg_counts = torch.empty(nranks, dtype=torch.int32, device=dev)
         seg_of = torch.empty((max(n_units, 1), nranks), dtype=torch.int32, device=dev)
         L.call("rf_pp_heads", L.ptr(ent[:, 1].contiguous()), n, L.ptr(counts), nranks, L.ptr(seg_counts), L.ptr(seg_of),
-               n_units, None, L.ptr(ws), wsb, L.stream_ptr(None))
+               n_units, None, L.ptr(ws), ws.numel(), L.stream_ptr(None))
         return ent, counts, seg_counts, seg_of
 
     def pp_owner_pool(self, desc, n_slots: int, ent: torch.Tensor, recv_counts: List[int], shard: torch.Tensor):
@@ -195,10 +191,9 @@ class GpuShardOps:
         cnt = torch.tensor(recv_counts, dtype=torch.int32).to(dev)
         seg_counts = torch.empty(P, dtype=torch.int32, device=dev)
         seg_start = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
-        wsb = int(L.load().rf_pp_ws_bytes(max(n, 1)))
-        ws = torch.empty(max(wsb, 256), dtype=torch.uint8, device=dev)
+        ws = L.workspace("rf_pp_ws_bytes", dev, max(n, 1))
         L.call("rf_pp_heads", L.ptr(ent[:, 1].contiguous()) if n else None, n, L.ptr(cnt), P, L.ptr(seg_counts), None, 0,
-               L.ptr(seg_start), L.ptr(ws), wsb, L.stream_ptr(None))
+               L.ptr(seg_start), L.ptr(ws), ws.numel(), L.stream_ptr(None))
         return seg_counts, seg_start
 
     def pp_owner_partials(self, desc, n_slots: int, ent, seg_start, n_seg: int, shard):
@@ -249,8 +244,7 @@ class GpuShardOps:
         grad = torch.empty((cap, D), dtype=torch.float32, device=self.device)
         n_uniq = torch.zeros(1, dtype=torch.int32, device=self.device)
         cnt = torch.empty(dout.shape, dtype=torch.int32, device=self.device) if need_minmax else None
-        wsb = int(L.load().rf_embed_bwd_ws_bytes(n_pos, n_slots, max(R, 1)))
-        ws = torch.empty(max(wsb, 256), dtype=torch.uint8, device=self.device)
+        ws = L.workspace("rf_embed_bwd_ws_bytes", self.device, n_pos, n_slots, max(R, 1))
         L.call("rf_pool_rows_bwd", L.ptr(desc), n_slots, L.ptr(batch.bag_off), L.ptr(batch.lmax), batch.batch,
                batch.n_tokens, n_pos, L.ptr(row_map), L.ptr(gathered), R, D, L.ptr(out) if need_minmax else None,
                L.ptr(dout), dout.stride(0), flags, L.ptr(cnt), L.ptr(rows), L.ptr(grad), cap, L.ptr(n_uniq), L.ptr(ws),
@@ -264,17 +258,7 @@ class GpuShardOps:
 
     def segment_sum(self, ids: torch.Tensor, vals: torch.Tensor, id_range: int):
         """rf_segment_sum_rows -> (distinct ids ascending, per-id sums in input order)."""
-        n = ids.numel()
-        D = vals.shape[1]
-        cap = max(1, min(n, id_range))
-        uid = torch.empty(cap, dtype=torch.int64, device=self.device)
-        uval = torch.empty((cap, D), dtype=torch.float32, device=self.device)
-        n_uniq = torch.zeros(1, dtype=torch.int32, device=self.device)
-        wsb = int(L.load().rf_segment_sum_ws_bytes(n, id_range))
-        ws = torch.empty(max(wsb, 256), dtype=torch.uint8, device=self.device)
-        L.call("rf_segment_sum_rows", L.ptr(ids.contiguous()), L.ptr(vals.contiguous()), n, D, id_range, L.ptr(uid),
-               L.ptr(uval), cap, L.ptr(n_uniq), L.ptr(ws), ws.numel(), L.stream_ptr(None))
-        return uid, uval, n_uniq, cap
+        return segment_sum_rows(ids, vals, id_range)
 
 
 class TorchDistComm:

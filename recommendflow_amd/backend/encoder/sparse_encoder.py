@@ -232,8 +232,7 @@ class FusedSparseEncoder(torch.nn.Module):
         if out is not None and (out.stride(0) != dout.stride(0) or out.dtype != torch.float32):
             out = out.contiguous().float()
         cnt = torch.empty(dout.shape, dtype=torch.int32, device=dev) if need_mm else None
-        wsb = L.load().rf_embed_bwd_ws_bytes(n_pos, len(self.slots), self.table.shape[0])
-        ws = torch.empty(max(int(wsb), 256), dtype=torch.uint8, device=dev)
+        ws = L.workspace("rf_embed_bwd_ws_bytes", dev, n_pos, len(self.slots), self.table.shape[0])
         flags = (L.FLAG_MASK_PADDING if self.mask_padding else 0) | (L.FLAG_TREE_REDUCE if self.tree_reduce else 0)
         L.call("rf_fused_hash_embed_bwd", L.ptr(self.desc), len(self.slots), L.ptr(batch.tok_bytes), L.ptr(batch.tok_off),
                L.ptr(batch.bag_off), L.ptr(batch.lmax), B, n_pos, L.ptr(self.table), self.table.shape[0], self.dim,
@@ -254,8 +253,7 @@ class FusedSparseEncoder(torch.nn.Module):
         cap = int(uniq_cap) if uniq_cap is not None else max(1, min(n_pos, self.table.shape[0]))
         rows = torch.empty(max(cap, 1), dtype=torch.int64, device=dev)
         n_uniq = torch.zeros(1, dtype=torch.int32, device=dev)
-        wsb = L.load().rf_embed_bwd_ws_bytes(n_pos, len(self.slots), self.table.shape[0])
-        ws = torch.empty(max(int(wsb), 256), dtype=torch.uint8, device=dev)
+        ws = L.workspace("rf_embed_bwd_ws_bytes", dev, n_pos, len(self.slots), self.table.shape[0])
         flags = (L.FLAG_MASK_PADDING if self.mask_padding else 0) | (L.FLAG_TREE_REDUCE if self.tree_reduce else 0)
         L.call("rf_fused_hash_embed_bwd_plan", L.ptr(self.desc), len(self.slots), L.ptr(batch.tok_bytes),
                L.ptr(batch.tok_off), L.ptr(batch.bag_off), L.ptr(batch.lmax), B, n_pos, self.table.shape[0], self.dim,

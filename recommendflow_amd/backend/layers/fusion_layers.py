@@ -79,8 +79,7 @@ class _FusionFn(torch.autograd.Function):
         dx = torch.empty_like(x)
         need_w = ctx.needs_input_grad[1]
         dW = torch.empty_like(W) if need_w else None
-        wsb = int(L.load().rf_attention_fusion_bwd_ws_bytes(B, channels, dim))
-        ws = torch.empty(wsb, dtype=torch.uint8, device=x.device)
+        ws = L.workspace("rf_attention_fusion_bwd_ws_bytes", x.device, B, channels, dim)
         if B == 0 and need_w:
             dW.zero_()
         L.call("rf_attention_fusion_bwd", L.ptr(x), B, channels, dim, x.stride(0), L.ptr(W), int(is_norm), L.ptr(att),

@@ -25,6 +25,7 @@ from typing import Dict, Optional, Sequence
 import torch
 
 from ...runtime import lib as L
+from ...runtime.segment import segment_sum_rows
 from .attention_layers import MultiHeadAttention
 from .core import Dense, LayerNormalization, Norm
 from .layer_utils import index_mapping
@@ -164,16 +165,28 @@ class CrossNetwork(torch.nn.Module):
             self.build(inputs.shape)
         if self.layer_num == 0:
             return inputs
-        x = inputs if inputs.dtype in (torch.float32, torch.bfloat16) else inputs.float()
-        if x.dim() != 2:
-            raise ValueError(f"expected [batch, dim], got {tuple(x.shape)}")
-        if x.shape[1] > 1 and x.stride(1) != 1:
-            x = x.contiguous()
-        B, dim = x.shape
-        out = torch.empty((B, dim), dtype=torch.float32, device=x.device)
-        L.call("rf_cross_fwd", L.ptr(x), L.torch_dtype_code(x.dtype), x.stride(0), B, dim, self.layer_num, L.ptr(self.w.data),
-               L.ptr(self.b.data), L.ptr(out), out.stride(0), L.stream_ptr())
-        return out
+        x = _cross_input(inputs)
+        return _cross_fwd(x, self.w.data, self.b.data, torch.empty(x.shape, dtype=torch.float32, device=x.device))
+
+
+def _cross_input(x: torch.Tensor) -> torch.Tensor:
+    """A [B, dim] view rf_cross_fwd reads in place: f32 or bf16, dim contiguous, any batch stride."""
+    if x.dtype not in (torch.float32, torch.bfloat16):
+        x = x.float()
+    if x.dim() != 2:
+        raise ValueError(f"expected [batch, dim], got {tuple(x.shape)}")
+    if x.shape[1] > 1 and x.stride(1) != 1:
+        x = x.contiguous()
+    return x
+
+
+def _cross_fwd(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+    """rf_cross_fwd of x [B, dim] through the layers w, b [layer_num, dim] into the left dim columns of out (F32, at
+    least dim wide: its row stride is the kernel's ldo)."""
+    B, dim = x.shape
+    L.call("rf_cross_fwd", L.ptr(x), L.torch_dtype_code(x.dtype), x.stride(0), B, dim, w.shape[0], L.ptr(w), L.ptr(b),
+           L.ptr(out), out.stride(0), L.stream_ptr())
+    return out
 
 
 class CIN(torch.nn.Module):
@@ -202,17 +215,22 @@ class CIN(torch.nn.Module):
             self.cin_W['CIN_W_' + str(i)] = torch.nn.Parameter(_normal(shape, g, self.device), requires_grad=False)
         self._packed = None
 
-    def refresh(self):
-        """Rebuild the bf16 kernel image from the fp32 master weights."""
+    def _pack(self, transposed: bool) -> torch.Tensor:
+        """The bf16 image of the fp32 master weights that rf_cin_fwd reads, or the transposed one of rf_cin_bwd."""
         K = len(self.cin_size)
-        nbytes = int(L.load().rf_cin_packed_w_bytes(self.embedding_nums, self._sizes, K))
-        if nbytes == 0:
-            L.check(L.RF_EINVAL, "rf_cin_packed_w_bytes")
-        packed = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        size_fn = "rf_cin_bwd_packed_w_bytes" if transposed else "rf_cin_packed_w_bytes"
+        packed = L.workspace(size_fn, self.device, self.embedding_nums, self._sizes, K, must=True)
         for i in range(K):
             W = self.cin_W['CIN_W_' + str(i)].data.float().contiguous()
-            L.call("rf_cin_pack_w", L.ptr(W), i, self.embedding_nums, self._sizes, K, L.ptr(packed), L.stream_ptr())
-        self._packed = packed
+            if transposed:
+                L.call("rf_cin_bwd_pack_w", L.ptr(W), i, self.embedding_nums, self._sizes, K, L.ptr(packed), L.stream_ptr())
+            else:
+                L.call("rf_cin_pack_w", L.ptr(W), i, self.embedding_nums, self._sizes, K, L.ptr(packed), L.stream_ptr())
+        return packed
+
+    def refresh(self):
+        """Rebuild the bf16 kernel image from the fp32 master weights."""
+        self._packed = self._pack(False)
 
     def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
         # not built yet: the first filter is (1, fields * fields, H_1), which gives the field count
@@ -231,16 +249,18 @@ class CIN(torch.nn.Module):
             raise ValueError(f"CIN was built for {self.embedding_nums} fields, got {fields}")
         if self._packed is None:
             self.refresh()
-        K = len(self.cin_size)
-        lib = L.load()
-        wsb = int(lib.rf_cin_ws_bytes(B, fields, dim, self._sizes, K))
-        if wsb == 0:
-            L.check(L.RF_EINVAL, "rf_cin_ws_bytes")
-        ws = torch.empty(wsb, dtype=torch.uint8, device=x.device)
-        out = torch.empty((B, sum(self.cin_size)), dtype=torch.float32, device=x.device)
-        L.call("rf_cin_fwd", L.ptr(x), L.torch_dtype_code(x.dtype), x.stride(0), x.stride(1), B, fields, dim, self._sizes, K,
-               L.ptr(self._packed), L.ptr(out), out.stride(0), L.ptr(ws), ws.numel(), L.stream_ptr())
-        return out
+        return _cin_fwd(x, self, torch.empty((B, sum(self.cin_size)), dtype=torch.float32, device=x.device))
+
+
+def _cin_fwd(x: torch.Tensor, layer: "CIN", out: torch.Tensor) -> torch.Tensor:
+    """rf_cin_fwd of x [B, fields, dim] through layer._packed into the left sum(cin_size) columns of out (F32, at least
+    that wide: its row stride is the kernel's ldo)."""
+    B, fields, dim = x.shape
+    K = len(layer.cin_size)
+    ws = L.workspace("rf_cin_ws_bytes", x.device, B, fields, dim, layer._sizes, K, must=True)
+    L.call("rf_cin_fwd", L.ptr(x), L.torch_dtype_code(x.dtype), x.stride(0), x.stride(1), B, fields, dim, layer._sizes, K,
+           L.ptr(layer._packed), L.ptr(out), out.stride(0), L.ptr(ws), ws.numel(), L.stream_ptr())
+    return out
 
 
 class FFN(torch.nn.Module):
@@ -314,29 +334,39 @@ class TransformerEncoder(torch.nn.Module):
         super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
         self.refresh()
 
-    def _pack_into(self, packed: torch.Tensor, block: int, n_blocks: int):
-        f = lambda name: L.ptr(getattr(self, name))  # noqa: E731
-        # Dense keeps [out][in]; the ABI takes the Keras (in, out) kernels
-        kern = {n: getattr(self, n).t().contiguous() for n in ("wq_kernel", "wk_kernel", "wv_kernel", "conv1_kernel", "conv2_kernel")}
-        L.call("rf_tfenc_pack", block, self.d_model, self.ffn_hidden_unit, n_blocks, L.ptr(kern["wq_kernel"]), f("wq_bias"),
-               L.ptr(kern["wk_kernel"]), f("wk_bias"), L.ptr(kern["wv_kernel"]), f("wv_bias"), f("ln1_gamma"), f("ln1_beta"),
-               L.ptr(kern["conv1_kernel"]), f("conv1_bias"), L.ptr(kern["conv2_kernel"]), f("conv2_bias"), f("ln2_gamma"),
-               f("ln2_beta"), L.ptr(packed), L.stream_ptr())
+    def _pack_into(self, packed: torch.Tensor, block: int, n_blocks: int, transposed: bool = False):
+        """This block's part of a stack's image (_tfenc_image): the fourteen masters for rf_tfenc_fwd, or, transposed,
+        the five kernels for rf_tfenc_bwd."""
+        with torch.no_grad():
+            src = [getattr(self, nm).detach() for nm in (_TFENC_KERNELS if transposed else _TFENC_ABI)]
+            # Dense keeps [out][in]; the ABI takes the Keras (in, out) kernels
+            src = [t.t().contiguous() if t.dim() == 2 else t for t in src]
+            ptrs = [L.ptr(t) for t in src]
+            if transposed:
+                L.call("rf_tfenc_bwd_pack", block, self.d_model, self.ffn_hidden_unit, n_blocks, *ptrs, L.ptr(packed),
+                       L.stream_ptr())
+            else:
+                L.call("rf_tfenc_pack", block, self.d_model, self.ffn_hidden_unit, n_blocks, *ptrs, L.ptr(packed),
+                       L.stream_ptr())
 
     def forward(self, inputs, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         x, mask = inputs
         return transformer_encoder_stack([self], x, mask, out=out)
 
 
-def transformer_encoder_stack(blocks: Sequence[TransformerEncoder], x: torch.Tensor, mask: Optional[torch.Tensor] = None,
-                              out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """blocks[-1](... blocks[0]([x, mask]) ..., mask) in ONE rf_tfenc_fwd launch through one packed image of all blocks
-    (cached on blocks[0] until one of them is refreshed or reloaded). The blocks must have equal shapes (d_model,
-    num_heads, ffn_hidden_unit, layer_norm_eps): ValueError otherwise."""
+# the order of rf_tfenc_pack's parameters and of rf_tfenc_bwd's grads, per block
+_TFENC_ABI = ("wq_kernel", "wq_bias", "wk_kernel", "wk_bias", "wv_kernel", "wv_bias", "ln1_gamma", "ln1_beta",
+              "conv1_kernel", "conv1_bias", "conv2_kernel", "conv2_bias", "ln2_gamma", "ln2_beta")
+# the five matrices among them, in the order of rf_tfenc_bwd_pack's parameters
+_TFENC_KERNELS = tuple(nm for nm in _TFENC_ABI if nm.endswith("_kernel"))
+
+
+def _tfenc_inputs(who: str, blocks, x: torch.Tensor, mask: Optional[torch.Tensor]):
+    """The checks of a stack and its inputs -> (blocks[0], len(blocks), x as rf_tfenc_fwd reads it, the mask as F32
+    [B, L] or None)."""
     L.require_gpu()
-    blocks = list(blocks)
     if not blocks:
-        raise ValueError("transformer_encoder_stack needs at least one block")
+        raise ValueError(f"{who} needs at least one block")
     lead = blocks[0]
     for blk in blocks[1:]:
         if blk.shape_key() != lead.shape_key():
@@ -345,62 +375,74 @@ def transformer_encoder_stack(blocks: Sequence[TransformerEncoder], x: torch.Ten
     B, Ln, d = x.shape
     if d != lead.d_model:
         raise ValueError(f"TransformerEncoder was built for d_model {lead.d_model}, got {d}")
-    n = len(blocks)
-    lib = L.load()
-    key = tuple((id(blk), blk._gen) for blk in blocks)
-    if lead._stack is None or lead._stack[0] != key:
-        nbytes = int(lib.rf_tfenc_packed_bytes(lead.d_model, lead.ffn_hidden_unit, n))
-        if nbytes == 0:
-            L.check(L.RF_EINVAL, "rf_tfenc_packed_bytes")
-        packed = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
-        for i, blk in enumerate(blocks):
-            blk._pack_into(packed, i, n)
-        lead._stack = (key, packed)
-    packed = lead._stack[1]
     m = None
     if mask is not None:
         m = mask.reshape(B, Ln).to(device=x.device, dtype=torch.float32).contiguous()
+    return lead, len(blocks), x, m
+
+
+def _tfenc_check_out(out: Optional[torch.Tensor], x: torch.Tensor):
+    B, Ln, d = x.shape
+    if out is not None and (out.dtype != torch.float32 or tuple(out.shape) != (B, Ln, d) or (d > 1 and out.stride(2) != 1)):
+        raise ValueError(f"out must be an F32 [{B}, {Ln}, {d}] view with unit stride on the last axis")
+
+
+def _tfenc_image(blocks, transposed: bool = False) -> torch.Tensor:
+    """The packed image of every block's fp32 masters: the one rf_tfenc_fwd reads (rf_tfenc_pack, all fourteen tensors),
+    or the bf16 copies of the five kernels that rf_tfenc_bwd reads beside it (rf_tfenc_bwd_pack)."""
+    lead, n = blocks[0], len(blocks)
+    size_fn = "rf_tfenc_bwd_packed_bytes" if transposed else "rf_tfenc_packed_bytes"
+    packed = L.workspace(size_fn, lead.wq_kernel.device, lead.d_model, lead.ffn_hidden_unit, n, must=True)
+    for i, blk in enumerate(blocks):
+        blk._pack_into(packed, i, n, transposed)
+    return packed
+
+
+def _tfenc_pack_transposed(blocks) -> torch.Tensor:
+    """rf_tfenc_bwd_pack: the bf16 copies of every block's five kernels that rf_tfenc_bwd reads, from the masters."""
+    return _tfenc_image(blocks, transposed=True)
+
+
+def _tfenc_fwd(lead: TransformerEncoder, n: int, x: torch.Tensor, m: Optional[torch.Tensor], packed: torch.Tensor,
+               out: Optional[torch.Tensor]) -> torch.Tensor:
+    """rf_tfenc_fwd of the n blocks in `packed` into out (checked by _tfenc_check_out), or into a new F32 [B, L, d]."""
+    B, Ln, d = x.shape
     if out is None:
         out = torch.empty((B, Ln, d), dtype=torch.float32, device=x.device)
-    elif out.dtype != torch.float32 or tuple(out.shape) != (B, Ln, d) or (d > 1 and out.stride(2) != 1):
-        raise ValueError(f"out must be an F32 [{B}, {Ln}, {d}] view with unit stride on the last axis")
     L.call("rf_tfenc_fwd", L.ptr(x), L.torch_dtype_code(x.dtype), x.stride(0), x.stride(1), L.ptr(m), B, Ln, d, lead.num_heads,
            lead.ffn_hidden_unit, n, L.ptr(packed), lead.layer_norm_eps, L.ptr(out), out.stride(0), out.stride(1),
            L.stream_ptr())
     return out
 
 
+def transformer_encoder_stack(blocks: Sequence[TransformerEncoder], x: torch.Tensor, mask: Optional[torch.Tensor] = None,
+                              out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """blocks[-1](... blocks[0]([x, mask]) ..., mask) in ONE rf_tfenc_fwd launch through one packed image of all blocks
+    (cached on blocks[0] until one of them is refreshed or reloaded). The blocks must have equal shapes (d_model,
+    num_heads, ffn_hidden_unit, layer_norm_eps): ValueError otherwise."""
+    blocks = list(blocks)
+    lead, n, x, m = _tfenc_inputs("transformer_encoder_stack", blocks, x, mask)
+    key = tuple((id(blk), blk._gen) for blk in blocks)
+    if lead._stack is None or lead._stack[0] != key:
+        lead._stack = (key, _tfenc_image(blocks))
+    _tfenc_check_out(out, x)
+    return _tfenc_fwd(lead, n, x, m, lead._stack[1], out)
+
+
 # ---- training ----------------------------------------------------------------------------------------------------------
-def _segment_sum(ids: torch.Tensor, vals: torch.Tensor, id_range: int):
-    """rf_segment_sum_rows: ids int64 [n], vals f32 [n, D] (D a multiple of 4, at most 256) -> (distinct ids ascending,
-    their rows summed in input order); ids outside [0, id_range) are dropped. Reads the device count (one sync)."""
-    n, D = vals.shape
-    cap = max(1, min(n, id_range))
-    dev = vals.device
-    uid = torch.empty(cap, dtype=torch.int64, device=dev)
-    uval = torch.empty((cap, D), dtype=torch.float32, device=dev)
-    n_uniq = torch.zeros(1, dtype=torch.int32, device=dev)
-    wsb = int(L.load().rf_segment_sum_ws_bytes(n, id_range))
-    ws = torch.empty(max(wsb, 256), dtype=torch.uint8, device=dev)
-    L.call("rf_segment_sum_rows", L.ptr(ids), L.ptr(vals), n, D, id_range, L.ptr(uid), L.ptr(uval), cap, L.ptr(n_uniq),
-           L.ptr(ws), ws.numel(), L.stream_ptr())
-    k = int(n_uniq.item())
-    return uid[:k], uval[:k]
-
-
 def _dense_row_grad(ids: torch.Tensor, vals: torch.Tensor, rows: int, width: int) -> torch.Tensor:
     """The dense [rows, width] gradient of a table from its per-position gradient rows vals [n, >= width] (columns past
-    `width` are padding to rf_segment_sum_rows' multiple of 4): per-id sums in position order, untouched rows zero."""
+    `width` are padding to rf_segment_sum_rows' multiple of 4): per-id sums in position order, untouched rows zero.
+    Reads the device count of distinct ids (one sync per 256 columns)."""
     out = torch.zeros((rows, width), dtype=torch.float32, device=vals.device)
-    ids = ids.reshape(-1).contiguous()
+    ids = ids.reshape(-1)
     for c0 in range(0, vals.shape[1], 256):
         blk = vals[:, c0: c0 + 256]
-        if vals.shape[1] > 256:
-            blk = blk.contiguous()
-        uid, uval = _segment_sum(ids, blk, rows)
+        uid, uval, n_uniq, _ = segment_sum_rows(ids, blk, rows)
+        k = int(n_uniq.item())
         w = min(width - c0, blk.shape[1])
         if w > 0:
-            out[uid, c0: c0 + w] = uval[:, :w]
+            out[uid[:k], c0: c0 + w] = uval[:k, :w]
     return out
 
 
@@ -478,9 +520,7 @@ class _CrossFn(torch.autograd.Function):
     def forward(ctx, x, w, b, right):
         B, dim = x.shape
         extra = 0 if right is None else right.shape[1]
-        out = torch.empty((B, dim + extra), dtype=torch.float32, device=x.device)
-        L.call("rf_cross_fwd", L.ptr(x), L.torch_dtype_code(x.dtype), x.stride(0), B, dim, w.shape[0], L.ptr(w), L.ptr(b),
-               L.ptr(out), out.stride(0), L.stream_ptr())
+        out = _cross_fwd(x, w, b, torch.empty((B, dim + extra), dtype=torch.float32, device=x.device))
         if right is not None:
             out[:, dim:] = right
         ctx.save_for_backward(x, w, b)
@@ -499,10 +539,7 @@ class _CrossFn(torch.autograd.Function):
         if B == 0:
             dw.zero_()
             db.zero_()
-        wsb = int(L.load().rf_cross_bwd_ws_bytes(B, dim, layers))
-        if wsb == 0:
-            L.check(L.RF_EINVAL, "rf_cross_bwd_ws_bytes")
-        ws = torch.empty(wsb, dtype=torch.uint8, device=x.device)
+        ws = L.workspace("rf_cross_bwd_ws_bytes", x.device, B, dim, layers, must=True)
         L.call("rf_cross_bwd", L.ptr(x), L.torch_dtype_code(x.dtype), x.stride(0), B, dim, layers, L.ptr(w), L.ptr(b),
                L.ptr(dout), dout.stride(0), L.ptr(dx), dx.stride(0), L.ptr(dw), L.ptr(db), L.ptr(ws), ws.numel(),
                L.stream_ptr())
@@ -573,12 +610,7 @@ class TrainCrossNetwork(CrossNetwork):
             self.build(inputs.shape)
         if self.layer_num == 0:
             return inputs if concat is None else torch.cat([inputs.float(), concat], dim=1)
-        x = inputs if inputs.dtype in (torch.float32, torch.bfloat16) else inputs.float()
-        if x.dim() != 2:
-            raise ValueError(f"expected [batch, dim], got {tuple(x.shape)}")
-        if x.shape[1] > 1 and x.stride(1) != 1:
-            x = x.contiguous()
-        return _CrossFn.apply(x, self.w, self.b, concat)
+        return _CrossFn.apply(_cross_input(inputs), self.w, self.b, concat)
 
     def regularization(self) -> torch.Tensor:
         return _l2(self.reg_w, self.w) + _l2(self.reg_b, self.b)
@@ -592,17 +624,9 @@ class _CinFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, layer, right, *Ws):
-        B, fields, dim = x.shape
-        K, sumH = len(layer.cin_size), sum(layer.cin_size)
+        sumH = sum(layer.cin_size)
         extra = 0 if right is None else right.shape[1]
-        lib = L.load()
-        wsb = int(lib.rf_cin_ws_bytes(B, fields, dim, layer._sizes, K))
-        if wsb == 0:
-            L.check(L.RF_EINVAL, "rf_cin_ws_bytes")
-        ws = torch.empty(wsb, dtype=torch.uint8, device=x.device)
-        out = torch.empty((B, sumH + extra), dtype=torch.float32, device=x.device)
-        L.call("rf_cin_fwd", L.ptr(x), L.torch_dtype_code(x.dtype), x.stride(0), x.stride(1), B, fields, dim, layer._sizes, K,
-               L.ptr(layer._packed), L.ptr(out), out.stride(0), L.ptr(ws), ws.numel(), L.stream_ptr())
+        out = _cin_fwd(x, layer, torch.empty((x.shape[0], sumH + extra), dtype=torch.float32, device=x.device))
         if right is not None:
             out[:, sumH:] = right
         ctx.save_for_backward(x)
@@ -623,11 +647,7 @@ class _CinFn(torch.autograd.Function):
         if B == 0:
             for d in dWs:
                 d.zero_()
-        lib = L.load()
-        wsb = int(lib.rf_cin_bwd_ws_bytes(B, fields, dim, layer._sizes, K))
-        if wsb == 0:
-            L.check(L.RF_EINVAL, "rf_cin_bwd_ws_bytes")
-        ws = torch.empty(wsb, dtype=torch.uint8, device=x.device)
+        ws = L.workspace("rf_cin_bwd_ws_bytes", x.device, B, fields, dim, layer._sizes, K, must=True)
         packed_t = layer._pack_transposed()
         ptrs = (ctypes.c_void_p * K)(*[d.data_ptr() for d in dWs])
         L.call("rf_cin_bwd", L.ptr(x), L.torch_dtype_code(x.dtype), x.stride(0), x.stride(1), B, fields, dim, layer._sizes, K,
@@ -658,15 +678,7 @@ class TrainCIN(CIN):
         return super().train(mode)
 
     def _pack_transposed(self) -> torch.Tensor:
-        K = len(self.cin_size)
-        nbytes = int(L.load().rf_cin_bwd_packed_w_bytes(self.embedding_nums, self._sizes, K))
-        if nbytes == 0:
-            L.check(L.RF_EINVAL, "rf_cin_bwd_packed_w_bytes")
-        packed = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-        for i in range(K):
-            W = self.cin_W['CIN_W_' + str(i)].data.float().contiguous()
-            L.call("rf_cin_bwd_pack_w", L.ptr(W), i, self.embedding_nums, self._sizes, K, L.ptr(packed), L.stream_ptr())
-        return packed
+        return self._pack(True)
 
     def forward(self, inputs: torch.Tensor, concat: Optional[torch.Tensor] = None) -> torch.Tensor:
         x = _dense_view(inputs)
@@ -683,28 +695,6 @@ class TrainCIN(CIN):
         return sum(_l2(self.l2_reg, p) for p in self.cin_W.values())
 
 
-# the order of rf_tfenc_pack's parameters and of rf_tfenc_bwd's grads, per block
-_TFENC_ABI = ("wq_kernel", "wq_bias", "wk_kernel", "wk_bias", "wv_kernel", "wv_bias", "ln1_gamma", "ln1_beta",
-              "conv1_kernel", "conv1_bias", "conv2_kernel", "conv2_bias", "ln2_gamma", "ln2_beta")
-
-
-def _tfenc_pack_transposed(blocks) -> torch.Tensor:
-    """rf_tfenc_bwd_pack: the bf16 copies of every block's five kernels that rf_tfenc_bwd reads, from the masters."""
-    lead, n = blocks[0], len(blocks)
-    nbytes = int(L.load().rf_tfenc_bwd_packed_bytes(lead.d_model, lead.ffn_hidden_unit, n))
-    if nbytes == 0:
-        L.check(L.RF_EINVAL, "rf_tfenc_bwd_packed_bytes")
-    packed = torch.empty(nbytes, dtype=torch.uint8, device=lead.wq_kernel.device)
-    with torch.no_grad():
-        for i, blk in enumerate(blocks):
-            # Dense keeps [out][in]; the ABI takes the Keras (in, out) kernels
-            kern = [getattr(blk, nm).detach().t().contiguous()
-                    for nm in ("wq_kernel", "wk_kernel", "wv_kernel", "conv1_kernel", "conv2_kernel")]
-            L.call("rf_tfenc_bwd_pack", i, lead.d_model, lead.ffn_hidden_unit, n, *[L.ptr(k) for k in kern], L.ptr(packed),
-                   L.stream_ptr())
-    return packed
-
-
 class _TfencFn(torch.autograd.Function):
     """out = rf_tfenc_fwd(x) over the whole stack (into `out` if given: a view of the caller's buffer, marked dirty, so
     that the gradient of whatever reads the buffer comes back here; autograd's in-place bookkeeping needs it to be the
@@ -714,15 +704,9 @@ class _TfencFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, out, x, blocks, mask, packed, *params):
-        B, Ln, d = x.shape
-        lead, n = blocks[0], len(blocks)
-        if out is None:
-            out = torch.empty((B, Ln, d), dtype=torch.float32, device=x.device)
-        else:
+        if out is not None:
             ctx.mark_dirty(out)
-        L.call("rf_tfenc_fwd", L.ptr(x), L.torch_dtype_code(x.dtype), x.stride(0), x.stride(1), L.ptr(mask), B, Ln, d,
-               lead.num_heads, lead.ffn_hidden_unit, n, L.ptr(packed), lead.layer_norm_eps, L.ptr(out), out.stride(0),
-               out.stride(1), L.stream_ptr())
+        out = _tfenc_fwd(blocks[0], len(blocks), x, mask, packed, out)
         ctx.save_for_backward(x, mask)
         ctx.blocks, ctx.packed = blocks, packed
         return out
@@ -741,14 +725,10 @@ class _TfencFn(torch.autograd.Function):
         if B == 0:  # an empty tensor keeps whatever strides it has
             dout = torch.empty((0, Ln, d), dtype=torch.float32, device=dev)
         dx = torch.empty((B, Ln, d), dtype=torch.float32, device=dev)
-        keras = {"wq_kernel": (d, d), "wk_kernel": (d, d), "wv_kernel": (d, d), "conv1_kernel": (d, ffn),
-                 "conv2_kernel": (ffn, d), "conv1_bias": (ffn,)}
         alloc = torch.zeros if B == 0 else torch.empty
-        grads = [alloc(keras.get(nm, (d,)), dtype=torch.float32, device=dev) for _ in blocks for nm in _TFENC_ABI]
-        wsb = int(L.load().rf_tfenc_bwd_ws_bytes(B, Ln, d, lead.num_heads, ffn, n))
-        if wsb == 0:
-            L.check(L.RF_EINVAL, "rf_tfenc_bwd_ws_bytes")
-        ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+        # in the Keras layouts: a master's shape reversed (Dense keeps its kernel as [out][in])
+        grads = [alloc(getattr(lead, nm).shape[::-1], dtype=torch.float32, device=dev) for _ in blocks for nm in _TFENC_ABI]
+        ws = L.workspace("rf_tfenc_bwd_ws_bytes", dev, B, Ln, d, lead.num_heads, ffn, n, must=True)
         packed_t = _tfenc_pack_transposed(blocks)
         ptrs = (ctypes.c_void_p * len(grads))(*[g.data_ptr() for g in grads])
         L.call("rf_tfenc_bwd", L.ptr(x), L.torch_dtype_code(x.dtype), x.stride(0), x.stride(1), L.ptr(mask), B, Ln, d,
@@ -790,8 +770,7 @@ class TrainTransformerEncoder(TransformerEncoder):
         return train_transformer_encoder_stack([self], x, mask, out=out)
 
     def regularization(self) -> torch.Tensor:
-        return sum(_l2(self.l2_reg, getattr(self, n)) for n in ("wq_kernel", "wk_kernel", "wv_kernel", "conv1_kernel",
-                                                                "conv2_kernel"))
+        return sum(_l2(self.l2_reg, getattr(self, n)) for n in _TFENC_KERNELS)
 
 
 def train_transformer_encoder_stack(blocks: Sequence[TrainTransformerEncoder], x: torch.Tensor,
@@ -800,43 +779,23 @@ def train_transformer_encoder_stack(blocks: Sequence[TrainTransformerEncoder], x
     if given, e.g. the left columns of a concat buffer viewed as [B, L, d_model]) and rf_tfenc_bwd backward. dx comes
     back in x's dtype, rounded once. With every block in eval mode, or without grad, it is transformer_encoder_stack."""
     blocks = list(blocks)
-    if not blocks:
-        raise ValueError("train_transformer_encoder_stack needs at least one block")
     training = any(blk.training for blk in blocks)
     if training:
         for blk in blocks:
             if blk.dropout > 0:
                 raise ValueError(f"TrainTransformerEncoder: dropout ({blk.dropout}) > 0 cannot be trained: rf_tfenc_fwd has "
                                  "no dropout")
-    if not training or not torch.is_grad_enabled():
+    if blocks and (not training or not torch.is_grad_enabled()):  # an empty stack is _tfenc_inputs' error below
         with torch.no_grad():
             if training:
                 for blk in blocks:
                     blk.refresh()
             return transformer_encoder_stack(blocks, x, mask, out=out)
-    L.require_gpu()
-    lead = blocks[0]
-    for blk in blocks[1:]:
-        if blk.shape_key() != lead.shape_key():
-            raise ValueError(f"blocks of one stack must have equal shapes: {blk.shape_key()} != {lead.shape_key()}")
-    x = _dense_view(x)
+    lead, n, x, m = _tfenc_inputs("train_transformer_encoder_stack", blocks, x, mask)
+    packed = _tfenc_image(blocks)  # on every forward: the optimizer writes the masters through raw pointers
     B, Ln, d = x.shape
-    if d != lead.d_model:
-        raise ValueError(f"TransformerEncoder was built for d_model {lead.d_model}, got {d}")
-    n = len(blocks)
-    nbytes = int(L.load().rf_tfenc_packed_bytes(lead.d_model, lead.ffn_hidden_unit, n))
-    if nbytes == 0:
-        L.check(L.RF_EINVAL, "rf_tfenc_packed_bytes")
     if int(L.load().rf_tfenc_bwd_ws_bytes(B, Ln, d, lead.num_heads, lead.ffn_hidden_unit, n)) == 0:
         L.check(L.RF_EINVAL, "rf_tfenc_bwd_ws_bytes")  # fail before the forward
-    packed = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
-    with torch.no_grad():
-        for i, blk in enumerate(blocks):
-            blk._pack_into(packed, i, n)
-    m = None
-    if mask is not None:
-        m = mask.reshape(B, Ln).to(device=x.device, dtype=torch.float32).contiguous()
-    if out is not None and (out.dtype != torch.float32 or tuple(out.shape) != (B, Ln, d) or (d > 1 and out.stride(2) != 1)):
-        raise ValueError(f"out must be an F32 [{B}, {Ln}, {d}] view with unit stride on the last axis")
+    _tfenc_check_out(out, x)
     params = [getattr(blk, nm) for blk in blocks for nm in _TFENC_ABI]
     return _TfencFn.apply(out, x, blocks, m, packed, *params)

@@ -13,10 +13,6 @@ import torch
 from ...runtime import lib as L
 
 
-def _ws(batch: int, device) -> torch.Tensor:
-    return torch.empty(max(int(L.load().rf_loss_ws_bytes(batch)), 256), dtype=torch.uint8, device=device)
-
-
 class _Cosent(torch.autograd.Function):
     @staticmethod
     def forward(ctx, score, label, scale):
@@ -25,7 +21,7 @@ class _Cosent(torch.autograd.Function):
         B = score.shape[0]
         loss = torch.empty((), dtype=torch.float32, device=score.device)
         ds = torch.empty_like(score)
-        ws = _ws(B, score.device)
+        ws = L.workspace("rf_loss_ws_bytes", score.device, B)
         L.call("rf_cosent_loss", L.ptr(score), L.ptr(label), B, float(scale), L.ptr(loss), L.ptr(ds), L.ptr(ws),
                ws.numel(), L.stream_ptr())
         ctx.save_for_backward(ds)
@@ -45,7 +41,7 @@ class _InBatchCE(torch.autograd.Function):
         B = logits.shape[0]
         loss = torch.empty((), dtype=torch.float32, device=logits.device)
         dl = torch.empty_like(logits)
-        ws = _ws(B, logits.device)
+        ws = L.workspace("rf_loss_ws_bytes", logits.device, B)
         L.call("rf_inbatch_ce_loss", L.ptr(logits), logits.stride(0), L.ptr(label), B, float(scale), L.ptr(loss),
                L.ptr(dl), dl.stride(0), L.ptr(ws), ws.numel(), L.stream_ptr())
         ctx.save_for_backward(dl)
@@ -75,7 +71,7 @@ class _CosineCosent(torch.autograd.Function):
         label = label.float().contiguous()
         loss = torch.empty((), dtype=torch.float32, device=a.device)
         ds = torch.empty_like(s)
-        ws = _ws(B, a.device)
+        ws = L.workspace("rf_loss_ws_bytes", a.device, B)
         L.call("rf_cosent_loss", L.ptr(s), L.ptr(label), B, float(scale), L.ptr(loss), L.ptr(ds), L.ptr(ws), ws.numel(),
                L.stream_ptr())
         ctx.save_for_backward(a, b, s, nrm, ds)

@@ -199,9 +199,8 @@ class FaissSearcher:
         n = assign.numel()
         list_off = torch.empty(self.nlist + 1, dtype=torch.int32, device=self.device)
         list_ids = torch.empty(n, dtype=torch.int32, device=self.device)  # item indices (< 2^31) as uint32
-        nb = int(L.load().rf_ivf_build_ws_bytes(n, self.nlist))
-        ws = torch.empty(max(nb, 4), dtype=torch.uint8, device=self.device)
-        L.call("rf_ivf_build_lists", L.ptr(assign), n, self.nlist, L.ptr(list_off), L.ptr(list_ids), L.ptr(ws), nb,
+        ws = L.workspace("rf_ivf_build_ws_bytes", self.device, n, self.nlist)
+        L.call("rf_ivf_build_lists", L.ptr(assign), n, self.nlist, L.ptr(list_off), L.ptr(list_ids), L.ptr(ws), ws.numel(),
                L.stream_ptr())
         return list_off, list_ids
 

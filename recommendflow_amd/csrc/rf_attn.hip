@@ -22,10 +22,10 @@
 #include <type_traits>
 
 #include "rf_common.h"
+#include "rf_wave.h"
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef short s4v __attribute__((ext_vector_type(4)));
 typedef short s8v __attribute__((ext_vector_type(8)));
@@ -386,15 +386,11 @@ __device__ __forceinline__ float rs4(float a, float b, float c, float d) {
 // Sum over each 32-lane half of the wave, in every lane of the half, without LDS: the 16-lane rows by DPP (quad_perm
 // [1,0,3,2], quad_perm [2,3,0,1], row_half_mirror, row_mirror), then rows 0 + 1 and 2 + 3 by one v_permlane16_swap
 // (a' = [r0, r0, r2, r2], b' = [r1, r1, r3, r3] for a = b = v)
-template <int CTRL>
-__device__ __forceinline__ float dpp_f(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
-}
 __device__ __forceinline__ float half32_sum(float v) {
-    v += dpp_f<0xB1>(v);
-    v += dpp_f<0x4E>(v);
-    v += dpp_f<0x141>(v);
-    v += dpp_f<0x140>(v);
+    v += dpp_mov<0xB1>(v);
+    v += dpp_mov<0x4E>(v);
+    v += dpp_mov<0x141>(v);
+    v += dpp_mov<0x140>(v);
     const auto p = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
     return __uint_as_float(p[0]) + __uint_as_float(p[1]);
 }

@@ -12,11 +12,11 @@
 #include <cstdlib>
 
 #include "rf_common.h"
+#include "rf_wave.h"
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f4 __attribute__((ext_vector_type(4)));
+typedef f32x4 f4;
 
 // GELU, exact form 0.5 x (1 + erf(x / sqrt 2)) (Keras 'gelu', approximate=False), without branches:
 // erfc(|z|) = t exp(-z^2 + P(t)), t = 1 / (1 + |z| / 2), P the Chebyshev fit of Numerical Recipes' erfcc
@@ -48,29 +48,6 @@ struct ActSelu {
         return x > 0.f ? scale * x : neg;
     }
 };
-
-// Sum over each 16-lane row of the wave, result in every lane of the row, by DPP (no LDS round trips):
-// quad_perm [1,0,3,2], quad_perm [2,3,0,1], row_half_mirror, row_mirror. Lane 0's value is bit-identical to
-// the xor butterfly (offsets 1, 2, 4, 8): every step adds the same two partial sums, only commuted.
-template <int CTRL>
-__device__ __forceinline__ float dpp_mov(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
-}
-__device__ __forceinline__ float row16_sum(float v) {
-    v += dpp_mov<0xB1>(v);   // quad_perm [1,0,3,2]
-    v += dpp_mov<0x4E>(v);   // quad_perm [2,3,0,1]
-    v += dpp_mov<0x141>(v);  // row_half_mirror
-    v += dpp_mov<0x140>(v);  // row_mirror
-    return v;
-}
-
-// Sum over the whole wave, the same bits in every lane: 16-lane rows by DPP, then rows (0+1) + (2+3)
-__device__ __forceinline__ float wave_sum(float v) {
-    v = row16_sum(v);
-    v += __shfl_xor(v, 16, 64);
-    v += __shfl_xor(v, 32, 64);
-    return v;
-}
 
 // Runs f(Act{}) with the activation resolved once, outside the element loops f contains.
 template <class F>
@@ -167,7 +144,7 @@ __global__ __launch_bounds__(256) void norm_vec_kernel(const float* __restrict__
         float s = 0.f;
 #pragma unroll
         for (int k = 0; k < NV; ++k) s += (v[k].x + v[k].y) + (v[k].z + v[k].w);
-        s = wave_sum(s);
+        s = wave_sum_row16_first(s);
         mu = s / (float)cols;
         float q = 0.f;
 #pragma unroll
@@ -177,7 +154,7 @@ __global__ __launch_bounds__(256) void norm_vec_kernel(const float* __restrict__
                 q += (a * a + b * b) + (c * c + d * d);
             }
         }
-        q = wave_sum(q);
+        q = wave_sum_row16_first(q);
         rstd = 1.0f / sqrtf(q / (float)cols + eps);
     }
 #pragma unroll
@@ -1304,7 +1281,7 @@ __global__ __launch_bounds__(256) void dense_head_kernel(const float* __restrict
 #pragma unroll
     for (int n = 0; n < NMAX; ++n) {
         if (n < N) {
-            acc[n] = wave_sum(acc[n]) + bv[n];
+            acc[n] = wave_sum_row16_first(acc[n]) + bv[n];
             if (act != RF_ACT_SOFTMAX) acc[n] = act_apply(act, acc[n]);
             mx = fmaxf(mx, acc[n]);
         }

@@ -12,16 +12,11 @@
 #include <algorithm>
 
 #include "rf_common.h"
+#include "rf_wave.h"
 
 namespace {
 
 constexpr int kMaxC = 16;
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 __global__ __launch_bounds__(256) void fusion_kernel(const float* __restrict__ x, int B, int C, int d, int64_t ldx,
                                                      const float* __restrict__ W, int is_norm, float* __restrict__ out,
@@ -45,7 +40,7 @@ __global__ __launch_bounds__(256) void fusion_kernel(const float* __restrict__ x
 #pragma unroll
     for (int c = 0; c < kMaxC; ++c)
         if (c < C) {
-            logit[c] = wave_sum(logit[c]);
+            logit[c] = wave_sum_butterfly(logit[c]);
             mx = fmaxf(mx, logit[c]);
         }
     float z = 0.f;
@@ -75,7 +70,7 @@ __global__ __launch_bounds__(256) void fusion_kernel(const float* __restrict__ x
     }
     if (is_norm) {
         // tf.nn.l2_normalize: x * rsqrt(max(sum(x^2), 1e-12))
-        const float inv = rsqrtf(fmaxf(wave_sum(ss), 1e-12f));
+        const float inv = rsqrtf(fmaxf(wave_sum_butterfly(ss), 1e-12f));
         for (int j = lane; j < d; j += 64) out[b * ldo + j] *= inv;
     }
 }
@@ -109,8 +104,8 @@ __global__ __launch_bounds__(256) void fusion_bwd_row_kernel(const float* __rest
             ss = fmaf(u, u, ss);
             ug = fmaf(u, gr[j], ug);
         }
-        ss = wave_sum(ss);
-        ug = wave_sum(ug);
+        ss = wave_sum_butterfly(ss);
+        ug = wave_sum_butterfly(ug);
         r = rsqrtf(fmaxf(ss, 1e-12f));
         coef = ss >= 1e-12f ? r * r * r * ug : 0.f;
     }
@@ -133,7 +128,7 @@ __global__ __launch_bounds__(256) void fusion_bwd_row_kernel(const float* __rest
     float sbar = 0.f;
 #pragma unroll
     for (int c = 0; c < C; ++c) {
-        s[c] = wave_sum(s[c]);
+        s[c] = wave_sum_butterfly(s[c]);
         sbar = fmaf(a[c], s[c], sbar);
     }
     if (lane < C) {

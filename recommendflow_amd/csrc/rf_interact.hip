@@ -31,17 +31,9 @@
 #include <algorithm>
 
 #include "rf_common.h"
+#include "rf_wave.h"
 
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 template <typename T>
 __device__ __forceinline__ float ld_f32(const T* p);
@@ -106,7 +98,7 @@ __global__ __launch_bounds__(256) void fm_kernel(const T* __restrict__ x, int64_
         }
         second += s * s - q;
     }
-    second = wave_sum(second);
+    second = wave_sum_butterfly(second);
     float first = 0.f;
     if (w) {
         const int64_t* wr = w_ids + b * ld_wids;
@@ -114,7 +106,7 @@ __global__ __launch_bounds__(256) void fm_kernel(const T* __restrict__ x, int64_
             const int64_t r = wr[i];
             first += r < 0 || r >= w_rows ? __uint_as_float(0x7fc00000u) : w[r];
         }
-        first = wave_sum(first);
+        first = wave_sum_butterfly(first);
     }
     if (lane == 0) out[b] = ((w0 ? *w0 : 0.f) + first) + 0.5f * second;
 }
@@ -148,7 +140,7 @@ __global__ __launch_bounds__(THREADS) void cross_kernel(const T* __restrict__ x,
             dot += xl[e] * (e < ne ? wl[tid + e * THREADS] : 0.f);
             if (e % 8 == 7) __builtin_amdgcn_sched_barrier(0);  // at most eight w loads in flight: no spills at EPT = 32
         }
-        dot = wave_sum(dot);
+        dot = wave_sum_butterfly(dot);
         if (lane == 0) red[l & 1][wave] = dot;  // two buffers: one barrier per layer is enough
         __syncthreads();
         float s = red[l & 1][0];
@@ -417,7 +409,7 @@ __global__ __launch_bounds__(256) void cross_bwd_const_kernel(const float* __res
 #pragma unroll
         for (int u = 0; u < 8; ++u) s += beta[u] * wv[u];
     }
-    s = wave_sum(s);
+    s = wave_sum_butterfly(s);
     if ((tid & 63) == 0) red[tid >> 6] = s;
     __syncthreads();
     if (tid == 0) t[l] = ((red[0] + red[1]) + red[2]) + red[3];
@@ -447,7 +439,7 @@ __global__ __launch_bounds__(THREADS) void cross_bwd_row_kernel(const T* __restr
         float dot = 0.f;
 #pragma unroll
         for (int e = 0; e < EPT; ++e) dot += g[e] * x0[e];
-        dot = wave_sum(dot);
+        dot = wave_sum_butterfly(dot);
         if (lane == 0) red[0][wave] = dot;
     }
     for (int m = 0; m < L; ++m) {
@@ -458,7 +450,7 @@ __global__ __launch_bounds__(THREADS) void cross_bwd_row_kernel(const T* __restr
             dot += x0[e] * (e < ne ? wm[tid + e * THREADS] : 0.f);
             if (e % 8 == 7) __builtin_amdgcn_sched_barrier(0);  // at most eight w loads in flight, as the forward
         }
-        dot = wave_sum(dot);
+        dot = wave_sum_butterfly(dot);
         if (lane == 0) red[m + 1][wave] = dot;
     }
     __syncthreads();
@@ -1038,20 +1030,6 @@ struct CinDzArgs {
     int64_t dsb, dsf, nr, n_sub;
     int F0, Hk, nj, nkh, dsub, D, layer0, first;
 };
-
-// Sum over each 16-lane row of the wave, in every lane of the row, by DPP (quad_perm [1,0,3,2], quad_perm [2,3,0,1],
-// row_half_mirror, row_mirror): four VALU operations, where a shuffle tree is four LDS round trips.
-template <int CTRL>
-__device__ __forceinline__ float dpp_f(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
-}
-__device__ __forceinline__ float row16_sum(float v) {
-    v += dpp_f<0xB1>(v);
-    v += dpp_f<0x4E>(v);
-    v += dpp_f<0x141>(v);
-    v += dpp_f<0x140>(v);
-    return v;
-}
 
 // NK: the layer's k steps over h (nkh) rounded up to a power of two. The wave's A fragments (G) stay in registers for
 // the whole kernel; the B fragments of UI fields are requested together, so that one trip to L2 is paid per UI fields

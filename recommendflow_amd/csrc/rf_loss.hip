@@ -14,21 +14,11 @@
 #include <algorithm>
 
 #include "rf_common.h"
+#include "rf_wave.h"
 
 namespace {
 
 constexpr int kRows = 256;  // i rows per block (one per thread)
-
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 // The B x B pairs run as (i block, j chunk) tiles: grid (ceil(B / 256), ceil(B / 64)), a thread per i walking its
 // tile's 64 j through LDS, so a 4096 batch fills 1,024 workgroups (a thread per i over every j kept 16 busy).
@@ -54,7 +44,7 @@ __global__ __launch_bounds__(kRows) void cosent_max_kernel(const float* __restri
         for (int k = 0; k < n; ++k)
             if (yi < yj[k]) m = fmaxf(m, scale * si - scale * sj[k]);
     }
-    m = wave_max(m);
+    m = wave_max_butterfly(m);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -68,7 +58,7 @@ __global__ __launch_bounds__(kRows) void cosent_max_kernel(const float* __restri
 __device__ __forceinline__ float cosent_m(const float* __restrict__ part, int nparts) {
     float m = 0.f;
     for (int p = threadIdx.x & 63; p < nparts; p += 64) m = fmaxf(m, part[p]);
-    return wave_max(m);
+    return wave_max_butterfly(m);
 }
 
 // pass B: per-tile partials of R_i and C_i with the global m
@@ -109,7 +99,7 @@ __global__ __launch_bounds__(kRows) void cosent_rows_kernel(const float* __restr
             c += Cp[(int64_t)t * B + i];
         }
     if (i < B) D[i] = r - c;
-    r = wave_sum(r);
+    r = wave_sum_butterfly(r);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = r;
     __syncthreads();
     if (threadIdx.x == 0) rpart[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
@@ -142,14 +132,14 @@ __global__ __launch_bounds__(256) void inbatch_ce_kernel(const float* __restrict
     const float* row = P + (int64_t)i * ld;
     float m = -INFINITY;
     for (int j = threadIdx.x; j < B; j += 256) m = fmaxf(m, scale * row[j]);
-    m = wave_max(m);
+    m = wave_max_butterfly(m);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
     __syncthreads();
     m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
     __syncthreads();
     float z = 0.f;
     for (int j = threadIdx.x; j < B; j += 256) z += expf(scale * row[j] - m);
-    z = wave_sum(z);
+    z = wave_sum_butterfly(z);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = z;
     __syncthreads();
     z = red[0] + red[1] + red[2] + red[3];
@@ -166,7 +156,7 @@ __global__ __launch_bounds__(1024) void mean_kernel(const float* __restrict__ v,
     __shared__ float red[16];
     float a = 0.f;
     for (int i = threadIdx.x; i < B; i += 1024) a += v[i];
-    a = wave_sum(a);
+    a = wave_sum_butterfly(a);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = a;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -222,9 +212,9 @@ __global__ __launch_bounds__(256) void cosine_rows_fwd_kernel(const float* __res
         bb += y * y;
         ab += x * y;
     }
-    aa = wave_sum(aa);
-    bb = wave_sum(bb);
-    ab = wave_sum(ab);
+    aa = wave_sum_butterfly(aa);
+    bb = wave_sum_butterfly(bb);
+    ab = wave_sum_butterfly(ab);
     if (lane == 0) {
         const float ra = sqrtf(aa), rb = sqrtf(bb);
         s[i] = ab / (fmaxf(ra, eps) * fmaxf(rb, eps));

@@ -42,12 +42,9 @@
 #include <cmath>
 
 #include "rf_common.h"
+#include "rf_wave.h"
 
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kTfMaxL = 256, kTfMaxD = 256, kTfMaxFfn = 1024, kTfMaxBlocks = 8, kTfMaxWaves = 8;
 constexpr size_t kTfMaxLds = 160 * 1024;
@@ -249,29 +246,6 @@ __device__ __forceinline__ void tf_st4(float* p, bool vec, f32x4 v) {
     }
 }
 
-__device__ __forceinline__ uint2 tf_pack4(f32x4 v) {
-    bf16x4 h;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) h[e] = (__bf16)v[e];
-    return __builtin_bit_cast(uint2, h);
-}
-
-__device__ __forceinline__ bf16x8 tf_join(uint2 lo, uint2 hi) {
-    return __builtin_bit_cast(bf16x8, make_uint4(lo.x, lo.y, hi.x, hi.y));
-}
-
-// sum / max over the four lane groups (g = lane >> 4) of one column: the same value in all four
-__device__ __forceinline__ float tf_gsum(float v) {
-    v += __shfl_xor(v, 16, 64);
-    v += __shfl_xor(v, 32, 64);
-    return v;
-}
-__device__ __forceinline__ float tf_gmax(float v) {
-    v = fmaxf(v, __shfl_xor(v, 16, 64));
-    v = fmaxf(v, __shfl_xor(v, 32, 64));
-    return v;
-}
-
 // LayerNorm over the d columns of each row of a transposed tile set r[t][e] = R[row lr][c = 16 t + 4 g + e]
 template <int ND>
 __device__ __forceinline__ void tf_layernorm(f32x4 (&r)[ND], int d, float eps, const float* gamma, const float* beta, int g) {
@@ -279,7 +253,7 @@ __device__ __forceinline__ void tf_layernorm(f32x4 (&r)[ND], int d, float eps, c
 #pragma unroll
     for (int t = 0; t < ND; ++t)
         if (16 * t < d) s += (r[t][0] + r[t][1]) + (r[t][2] + r[t][3]);
-    const float mean = tf_gsum(s) / (float)d;
+    const float mean = rows4_sum(s) / (float)d;
     float q = 0.f;
 #pragma unroll
     for (int t = 0; t < ND; ++t)
@@ -287,7 +261,7 @@ __device__ __forceinline__ void tf_layernorm(f32x4 (&r)[ND], int d, float eps, c
             const float a = r[t][0] - mean, b = r[t][1] - mean, c = r[t][2] - mean, e = r[t][3] - mean;
             q += (a * a + b * b) + (c * c + e * e);
         }
-    const float inv = 1.f / sqrtf(tf_gsum(q) / (float)d + eps);
+    const float inv = 1.f / sqrtf(rows4_sum(q) / (float)d + eps);
 #pragma unroll
     for (int t = 0; t < ND; ++t) {
         const f32x4 ga = *reinterpret_cast<const f32x4*>(gamma + 16 * t + 4 * g);
@@ -357,8 +331,8 @@ __global__ __launch_bounds__(64 * kTfMaxWaves) void tfenc_kernel(const TfArgs a)
                     ak[e] += kb[e];
                     av[e] += vb;
                 }
-                *reinterpret_cast<uint2*>(Kl + (size_t)j * pK + 16 * ct + 4 * g) = tf_pack4(ak);
-                *reinterpret_cast<uint2*>(Vl + (size_t)(16 * ct + lr) * pV + 16 * jt + 4 * g) = tf_pack4(av);
+                *reinterpret_cast<uint2*>(Kl + (size_t)j * pK + 16 * ct + 4 * g) = bf16_pack4(ak);
+                *reinterpret_cast<uint2*>(Vl + (size_t)(16 * ct + lr) * pV + 16 * jt + 4 * g) = bf16_pack4(av);
             }
         }
         __syncthreads();
@@ -397,13 +371,13 @@ __global__ __launch_bounds__(64 * kTfMaxWaves) void tfenc_kernel(const TfArgs a)
                         q0[e] += qb0[e];
                         q1[e] = two ? q1[e] + qb1[e] : 0.f;
                     }
-                    const bf16x8 qf = tf_join(tf_pack4(q0), tf_pack4(q1));
+                    const bf16x8 qf = bf16_join(bf16_pack4(q0), bf16_pack4(q1));
                     const uint16_t* kcol = Kl + c0 + 32 * s2 + 4 * g;
                     const int hi = two ? 16 : 0;  // one tile: the upper half of the step multiplies zeros
 #pragma unroll
                     for (int jt = 0; jt < NT2; ++jt) {
                         const uint16_t* kp = kcol + (size_t)min(16 * jt + lr, Lr - 1) * pK;  // past Lr: any row, logit -inf
-                        const bf16x8 kf = tf_join(*reinterpret_cast<const uint2*>(kp), *reinterpret_cast<const uint2*>(kp + hi));
+                        const bf16x8 kf = bf16_join(*reinterpret_cast<const uint2*>(kp), *reinterpret_cast<const uint2*>(kp + hi));
                         S[jt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf, S[jt], 0, 0, 0);  // S^T[j = 4 g + r][i = lr]
                     }
                 }
@@ -418,7 +392,7 @@ __global__ __launch_bounds__(64 * kTfMaxWaves) void tfenc_kernel(const TfArgs a)
                         S[jt][r] = l;
                         m = fmaxf(m, l);
                     }
-                m = tf_gmax(m);
+                m = rows4_max(m);
                 float sum = 0.f;
 #pragma unroll
                 for (int jt = 0; jt < NT2; ++jt)
@@ -427,7 +401,7 @@ __global__ __launch_bounds__(64 * kTfMaxWaves) void tfenc_kernel(const TfArgs a)
                         S[jt][r] = __expf(S[jt][r] - m);
                         sum += S[jt][r];
                     }
-                const float inv = 1.f / tf_gsum(sum);
+                const float inv = 1.f / rows4_sum(sum);
                 bf16x8 P[NJ];
 #pragma unroll
                 for (int s = 0; s < NJ; ++s) {
@@ -437,7 +411,7 @@ __global__ __launch_bounds__(64 * kTfMaxWaves) void tfenc_kernel(const TfArgs a)
                         lo[r] = S[2 * s][r] * inv;
                         hi[r] = S[2 * s + 1][r] * inv;
                     }
-                    P[s] = tf_join(tf_pack4(lo), tf_pack4(hi));
+                    P[s] = bf16_join(bf16_pack4(lo), bf16_pack4(hi));
                 }
                 // att^T = V^T P^T per 16 columns of the head, + x, to the tile's rows of out
                 for (int tt = 0; tt < nt; ++tt) {
@@ -447,7 +421,7 @@ __global__ __launch_bounds__(64 * kTfMaxWaves) void tfenc_kernel(const TfArgs a)
 #pragma unroll
                     for (int s = 0; s < NJ; ++s) {
                         const int j0 = 32 * s < Lr ? 32 * s : 0;  // past Lr: P is exactly zero, any finite v
-                        const bf16x8 vf = tf_join(*reinterpret_cast<const uint2*>(vp + j0),
+                        const bf16x8 vf = bf16_join(*reinterpret_cast<const uint2*>(vp + j0),
                                                   *reinterpret_cast<const uint2*>(vp + j0 + 16));
                         acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, P[s], acc, 0, 0, 0);  // att^T[c = 4 g + r][i = lr]
                     }
@@ -479,8 +453,8 @@ __global__ __launch_bounds__(64 * kTfMaxWaves) void tfenc_kernel(const TfArgs a)
 #pragma unroll
             for (int s = 0; s < KS; ++s) {
                 uint2 hi2 = make_uint2(0u, 0u);
-                if constexpr (ND > 1) hi2 = tf_pack4(o1[2 * s + (ND > 1 ? 1 : 0)]);
-                of[s] = tf_join(tf_pack4(o1[2 * s]), hi2);
+                if constexpr (ND > 1) hi2 = bf16_pack4(o1[2 * s + (ND > 1 ? 1 : 0)]);
+                of[s] = bf16_join(bf16_pack4(o1[2 * s]), hi2);
             }
             // FFN, 32 hidden units at a time
             f32x4 y[ND];
@@ -503,7 +477,7 @@ __global__ __launch_bounds__(64 * kTfMaxWaves) void tfenc_kernel(const TfArgs a)
                     h0[e] = fmaxf(h0[e] + hb0[e], 0.f);
                     h1[e] = fmaxf(h1[e] + hb1[e], 0.f);
                 }
-                const bf16x8 hf = tf_join(tf_pack4(h0), tf_pack4(h1));
+                const bf16x8 hf = bf16_join(bf16_pack4(h0), bf16_pack4(h1));
 #pragma unroll
                 for (int t = 0; t < ND; ++t) {
                     const bf16x8 w2 = __builtin_bit_cast(bf16x8, W2[(t * nfs + fs) * 64 + lane]);

@@ -38,12 +38,9 @@
 #include <cmath>
 
 #include "rf_common.h"
+#include "rf_wave.h"
 
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kTbChunks = 64;          // at most this many row chunks ...
 constexpr int64_t kTbMinChunk = 1024;  // ... of at least this many rows
@@ -143,31 +140,9 @@ __device__ __forceinline__ bf16x8 tb_ld8(const float* p) {
     f[4] = (__bf16)b.x; f[5] = (__bf16)b.y; f[6] = (__bf16)b.z; f[7] = (__bf16)b.w;
     return f;
 }
-__device__ __forceinline__ uint2 tb_pack4(f32x4 v) {
-    bf16x4 h;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) h[e] = (__bf16)v[e];
-    return __builtin_bit_cast(uint2, h);
-}
-__device__ __forceinline__ bf16x8 tb_join(uint2 lo, uint2 hi) { return __builtin_bit_cast(bf16x8, make_uint4(lo.x, lo.y, hi.x, hi.y)); }
 // Every MFMA here is issued unconditionally (tiles past L or Lp run on clamped addresses and are masked or multiply exact
 // zeros): a product under a branch came back with two of its four accumulator rows read before the MFMA had written them
 // (the compiler places the wait states between an MFMA and the read of its result only inside one basic block).
-__device__ __forceinline__ float tb_gsum(float v) {
-    v += __shfl_xor(v, 16, 64);
-    v += __shfl_xor(v, 32, 64);
-    return v;
-}
-__device__ __forceinline__ float tb_gmax(float v) {
-    v = fmaxf(v, __shfl_xor(v, 16, 64));
-    v = fmaxf(v, __shfl_xor(v, 32, 64));
-    return v;
-}
-__device__ __forceinline__ float tb_wsum(float v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 // ---- the transposed image ---------------------------------------------------------------------------------------------
 struct TbPackArgs {
@@ -294,7 +269,7 @@ __global__ __launch_bounds__(64) void tfb_rowgemm(const RgArgs a) {
 #pragma unroll
                 for (int e = 0; e < 4; ++e) v[e] = bf16_bits_to_f32(h[e]) > 0.f ? v[e] : 0.f;
             }
-            *reinterpret_cast<uint2*>(static_cast<uint16_t*>(a.out) + row * a.N + n) = tb_pack4(v);
+            *reinterpret_cast<uint2*>(static_cast<uint16_t*>(a.out) + row * a.N + n) = bf16_pack4(v);
         }
     }
 }
@@ -336,7 +311,7 @@ struct AtArgs {
 };
 
 __device__ __forceinline__ bf16x8 tb_ld44(const uint16_t* p) {
-    return tb_join(*reinterpret_cast<const uint2*>(p), *reinterpret_cast<const uint2*>(p + 16));
+    return bf16_join(*reinterpret_cast<const uint2*>(p), *reinterpret_cast<const uint2*>(p + 16));
 }
 
 template <int NJ, int MODE>
@@ -397,7 +372,7 @@ __global__ __launch_bounds__(64) void tfb_attn(const AtArgs a) {
                 S[ot][r] = l;
                 m = fmaxf(m, l);
             }
-        m = tb_gmax(m);
+        m = rows4_max(m);
         float sum = 0.f;
 #pragma unroll
         for (int ot = 0; ot < NT2; ++ot)
@@ -406,7 +381,7 @@ __global__ __launch_bounds__(64) void tfb_attn(const AtArgs a) {
                 S[ot][r] = __expf(S[ot][r] - m);
                 sum += S[ot][r];
             }
-        const float inv = 1.f / tb_gsum(sum);
+        const float inv = 1.f / rows4_sum(sum);
 #pragma unroll
         for (int ot = 0; ot < NT2; ++ot)
 #pragma unroll
@@ -414,7 +389,7 @@ __global__ __launch_bounds__(64) void tfb_attn(const AtArgs a) {
         bf16x8 F[NJ];
         if constexpr (MODE == 0) {
 #pragma unroll
-            for (int s = 0; s < NJ; ++s) F[s] = tb_join(tb_pack4(S[2 * s]), tb_pack4(S[2 * s + 1]));
+            for (int s = 0; s < NJ; ++s) F[s] = bf16_join(bf16_pack4(S[2 * s]), bf16_pack4(S[2 * s + 1]));
             for (int tt = 0; tt < nt; ++tt) {
                 const uint16_t* vp = a.qkvT + ((b * ld + vCol + 16 * tt + lr) * Lp + 4 * g);
                 f32x4 acc = {0.f, 0.f, 0.f, 0.f};
@@ -435,13 +410,13 @@ __global__ __launch_bounds__(64) void tfb_attn(const AtArgs a) {
             for (int ot = 0; ot < NT2; ++ot)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) ds += dP[ot][r] * S[ot][r];
-            const float delta = tb_gsum(ds);
+            const float delta = rows4_sum(ds);
 #pragma unroll
             for (int ot = 0; ot < NT2; ++ot)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) dP[ot][r] = masked ? 0.f : S[ot][r] * (dP[ot][r] - delta) * a.scale;
 #pragma unroll
-            for (int s = 0; s < NJ; ++s) F[s] = tb_join(tb_pack4(dP[2 * s]), tb_pack4(dP[2 * s + 1]));
+            for (int s = 0; s < NJ; ++s) F[s] = bf16_join(bf16_pack4(dP[2 * s]), bf16_pack4(dP[2 * s + 1]));
             if (live && g == 0) {
                 st_m[sidx] = m;
                 st_i[sidx] = inv;
@@ -453,7 +428,7 @@ __global__ __launch_bounds__(64) void tfb_attn(const AtArgs a) {
 #pragma unroll
                 for (int s = 0; s < NJ; ++s)
                     acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(tb_ld44(kp + (32 * s < Lp ? 32 * s : 0)), F[s], acc, 0, 0, 0);
-                            if (live) *reinterpret_cast<uint2*>(a.dqkv + (b * L + sidx) * ld + c0 + 16 * tt + 4 * g) = tb_pack4(acc);
+                            if (live) *reinterpret_cast<uint2*>(a.dqkv + (b * L + sidx) * ld + c0 + 16 * tt + 4 * g) = bf16_pack4(acc);
             }
         }
     } else {
@@ -480,8 +455,8 @@ __global__ __launch_bounds__(64) void tfb_attn(const AtArgs a) {
             }
 #pragma unroll
         for (int s = 0; s < NJ; ++s) {
-            FP[s] = tb_join(tb_pack4(S[2 * s]), tb_pack4(S[2 * s + 1]));
-            FD[s] = tb_join(tb_pack4(dP[2 * s]), tb_pack4(dP[2 * s + 1]));
+            FP[s] = bf16_join(bf16_pack4(S[2 * s]), bf16_pack4(S[2 * s + 1]));
+            FD[s] = bf16_join(bf16_pack4(dP[2 * s]), bf16_pack4(dP[2 * s + 1]));
         }
         for (int tt = 0; tt < nt; ++tt) {
             const uint16_t* ap = a.dattT + ((b * d + c0 + 16 * tt + lr) * Lp + 4 * g);
@@ -496,8 +471,8 @@ __global__ __launch_bounds__(64) void tfb_attn(const AtArgs a) {
             }
                     if (live) {
                 uint16_t* o = a.dqkv + (b * L + sidx) * ld + c0 + 16 * tt + 4 * g;
-                *reinterpret_cast<uint2*>(o + d) = tb_pack4(ak);
-                *reinterpret_cast<uint2*>(o + 2 * d) = tb_pack4(av);
+                *reinterpret_cast<uint2*>(o + d) = bf16_pack4(ak);
+                *reinterpret_cast<uint2*>(o + 2 * d) = bf16_pack4(av);
             }
         }
     }
@@ -516,14 +491,14 @@ __global__ __launch_bounds__(256) void tfb_ln_fwd(const float* r, const float* g
         v[e] = c < d ? r[row * d + c] : 0.f;
         s += v[e];
     }
-    const float mean = tb_wsum(s) / (float)d;
+    const float mean = wave_sum_butterfly(s) / (float)d;
     float q = 0.f;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
         const float t = lane + 64 * e < d ? v[e] - mean : 0.f;
         q += t * t;
     }
-    const float inv = 1.f / sqrtf(tb_wsum(q) / (float)d + eps);
+    const float inv = 1.f / sqrtf(wave_sum_butterfly(q) / (float)d + eps);
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
         const int c = lane + 64 * e;
@@ -548,14 +523,14 @@ __global__ __launch_bounds__(256) void tfb_ln_bwd(const float* r, const float* d
         gy[e] = c < d ? dyv[e] * gamma[c] : 0.f;
         s += v[e];
     }
-    const float mean = tb_wsum(s) / (float)d;
+    const float mean = wave_sum_butterfly(s) / (float)d;
     float q = 0.f;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
         v[e] = lane + 64 * e < d ? v[e] - mean : 0.f;
         q += v[e] * v[e];
     }
-    const float inv = 1.f / sqrtf(tb_wsum(q) / (float)d + eps);
+    const float inv = 1.f / sqrtf(wave_sum_butterfly(q) / (float)d + eps);
     float s1 = 0.f, s2 = 0.f;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
@@ -563,7 +538,7 @@ __global__ __launch_bounds__(256) void tfb_ln_bwd(const float* r, const float* d
         s1 += gy[e];
         s2 += gy[e] * v[e];
     }
-    const float m1 = tb_wsum(s1) / (float)d, m2 = tb_wsum(s2) / (float)d;
+    const float m1 = wave_sum_butterfly(s1) / (float)d, m2 = wave_sum_butterfly(s2) / (float)d;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
         const int c = lane + 64 * e;

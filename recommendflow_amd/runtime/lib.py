@@ -256,6 +256,17 @@ def call(name: str, *args):
     return rc
 
 
+def workspace(size_fn: str, device, *args, must: bool = False):
+    """A uint8 buffer of the named rf_*_bytes entry's size for `args` (a workspace or a packed image), at least 256
+    bytes. must: a size of 0 is how the entry reports an invalid shape: ValueError with rf_last_error's message."""
+    import torch
+
+    n = int(getattr(load(), size_fn)(*args))
+    if must and n == 0:
+        check(RF_EINVAL, size_fn)
+    return torch.empty(max(n, 256), dtype=torch.uint8, device=device)
+
+
 def torch_dtype_code(dtype) -> int:
     import torch
 

@@ -54,6 +54,29 @@ def test_argument_errors_without_gpu():
     assert lib.rf_bucketize_ws_bytes(1000, 8) >= 2 * 4 * 8 * 4
 
 
+def test_workspace_sizes_allocates_and_reports_invalid_shapes():
+    """L.workspace: the named rf_*_bytes entry sizes the buffer, with a floor of 256 bytes; must=True turns the entry's
+    0 (an invalid shape, the reason in rf_last_error) into a ValueError that names the entry."""
+    import pytest
+    import torch
+
+    lib = L.load()
+    sizes = (ctypes.c_int32 * 1)(4)
+    need = int(lib.rf_cin_ws_bytes(2, 3, 8, sizes, 1))
+    assert need > 0
+    ws = L.workspace("rf_cin_ws_bytes", "cpu", 2, 3, 8, sizes, 1, must=True)
+    assert ws.dtype == torch.uint8 and ws.dim() == 1 and ws.numel() >= need
+    with pytest.raises(ValueError, match="rf_cin_ws_bytes") as e:
+        L.workspace("rf_cin_ws_bytes", "cpu", 2, 0, 8, sizes, 1, must=True)
+    assert "fields" in str(e.value)  # rf_last_error's text reaches the caller
+    small = int(lib.rf_tower_ws_bytes(1, 4))
+    assert 0 < small < 256
+    assert L.workspace("rf_tower_ws_bytes", "cpu", 1, 4).numel() == 256
+    big = int(lib.rf_segment_sum_ws_bytes(1000, 1000))
+    assert big > 256 and L.workspace("rf_segment_sum_ws_bytes", "cpu", 1000, 1000).numel() == big
+    assert L.workspace("rf_cin_ws_bytes", "cpu", 2, 0, 8, sizes, 1).numel() == 256  # without must: no error
+
+
 def test_product_path_has_no_oracle_import():
     pkg = os.path.join(ROOT, "recommendflow_amd")
     for dirpath, _, files in os.walk(pkg):
